@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Headline benchmark: mic-pair GCC-PHAT correlations per second on 44.1 kHz x 1 s frames.
 
-    python bench.py --gpus 1 --steps K --warmup W                        # the metric workload (BASELINE.json)
+    python bench.py --gpus 1 --steps K --warmup W                        # the metric workload (BASELINE.json), headline only
+    python bench.py --gpus 1 --steps K --warmup W --full                 # + rooflines, per-kernel times, CPU baseline, parity sample
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     # + the last timed step's pair table as DIR/<field>.npy
     python bench.py --config {c2,c3,c4,c5} ...                           # the other BASELINE configurations, same path
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
@@ -12,11 +14,12 @@ independent, so N ranks (one process per GPU) each own their frames - weak scali
 every step ends with ONE all-gather of the 48-byte-per-pair TDOA tables (RCCL over xGMI through the engine's own
 communicator; torch.distributed / gloo only carries the barrier, the unique id and the max-over-ranks of the time).
 
-Rank 0 prints one JSON line.  `roofline` is the HBM roofline BASELINE.json asks for: `frac` is the WHOLE JOB
-(pairs/s x algorithmic bytes per pair / 8 TB/s); the dominant kernel is priced beside it with its own compulsory
-bytes and its duration from a single-stream calibration pass.  `roofline_fp64` prices the same run against the
-fp64 vector rate, which is what actually binds this path.  `cpu_baseline` times the NumPy
-oracle (the reference's pocketfft calls) on one core and on all cores of the box, BEFORE the GPU is touched.
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the steps and reports the rate and `ms_per_step`;
+the blocks below are filled only with `--full` (null otherwise).  `roofline` is the HBM roofline BASELINE.json asks
+for: `frac` is the WHOLE JOB (pairs/s x algorithmic bytes per pair / 8 TB/s); the dominant kernel is priced beside it
+with its own compulsory bytes and its duration from a single-stream calibration pass.  `roofline_fp64` prices the same
+run against the fp64 vector rate, which is what actually binds this path.  `cpu_baseline` times
+the NumPy oracle (the reference's pocketfft calls) on one core and on all cores of the box, BEFORE the GPU is touched.
 """
 from __future__ import annotations
 
@@ -205,6 +208,26 @@ def traffic_lookup(table, name):
     return None
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(path: str, table: np.ndarray, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """The pair table a caller of the timed path receives, one float64 array per record field: path/<field>.npy shaped
+    like the table (the integer fields are exact in float64).  A table above `limit` bytes in all is replaced by a fixed
+    sample of its records (seed 0, flat indices in ascending order, written as path/sample_index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    names = table.dtype.names
+    flat = table.reshape(-1)
+    shape = table.shape
+    if flat.size * 8 * len(names) > limit:
+        keep = (limit - 4096) // (8 * (len(names) + 1))              # (+1: the index array; 4096: the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(flat.size, keep, replace=False))
+        flat, shape = flat[idx], (keep,)
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+    for name in names:
+        np.save(os.path.join(path, f"{name}.npy"), flat[name].astype(np.float64).reshape(shape))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -226,7 +249,14 @@ def main() -> None:
                     help="frames: every rank owns its own frames (weak scaling); pairs: ONE frame's ordered pair list is block-partitioned "
                          "over the ranks, spectra recomputed on every rank (strong scaling of a single large frame, SURVEY 8e: C4)")
     ap.add_argument("--require-rccl", action="store_true", help="exit non-zero when the per-step gather cannot run on RCCL (N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baseline, HIP events around the kernels, the calibration "
+                         "pass, rooflines, parity sample (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the pair table of the last timed step as DIR/<field>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -247,7 +277,7 @@ def main() -> None:
 
     # ---- CPU baseline first: host cores only, before this process initialises the GPU -------------------------------
     cpu, want, cm = None, None, 0
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, want, cm = cpu_baseline(frames[0], fs, med, args.cpu_mics if args.config == "metric" else min(args.cpu_mics, 12))
 
     from pyaudiolocalization_amd import Engine, RECORD, make_params, pair_list
@@ -332,17 +362,18 @@ def main() -> None:
             dist.barrier()
         eng.synchronize()
 
+    events = args.full and not args.no_kernel_events
     for _ in range(args.warmup):
         step()
     barrier()
-    if not args.no_kernel_events:
+    if events:
         eng.profile_begin(every=args.event_every)   # HIP events around a sample of the launch groups (they cost idle stream time)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     elapsed = time.perf_counter() - t0
-    if not args.no_kernel_events:
+    if events:
         eng.profile_end()
     if dist is not None:
         import torch
@@ -364,139 +395,149 @@ def main() -> None:
             if full is not None and len(full) != b * world:
                 raise RuntimeError("gathered table has the wrong number of frames")
         gather += " - once, after the timed region"
+    if args.dump_outputs and rank == 0:
+        out = host_table
+        if gather == "rccl-allgather":                              # every rank's table of the last step, gathered on device
+            out = np.zeros((world * host_table.shape[0],) + host_table.shape[1:], dtype=RECORD)
+            eng.download(out, d_all)
+        elif gather.startswith("gloo-host"):
+            out = full
+        dump_outputs(args.dump_outputs, out)
     total_pairs = args.steps * (pairs if split_pairs else b * pairs * world)     # pairs: the ONE frame's list, whatever the rank count
     value = total_pairs / elapsed
 
-    # ---- per-kernel durations: live (HIP events inside the timed region, three streams share the CUs) and alone
-    #      (one untimed calibration frame on a second, single-stream engine: PAL_OVERLAP=0, events around every launch)
-    entries = eng.profile_entries()
-    kernels = {k: {"ms": round(v[0], 3), "launches": v[1]} for k, v in entries.items() if v[1] > 0}
-    alone, alone_avg = {}, {}
-    cal_pairs_per_launch = 0.0
-    if rank == 0 and entries:
-        saved = os.environ.get("PAL_OVERLAP")
-        os.environ["PAL_OVERLAP"] = "0"
-        cal = None
-        try:
-            cal = Engine(0 if share else local_rank)
-            cb = 1 if split_pairs else min(b, max(1, -(-2 * eng.pair_group_size(length) // pairs)))       # frames that fill one launch group
-            one = frames[:cb]
-            d_one, d_tab = cal.alloc(one.nbytes), cal.alloc(cb * pairs * RECORD.itemsize)
-            cal.upload(d_one, one)
-            cal.gcc_phat_all_pairs_dev(d_one, cb, m, length, prm, d_tab)      # plans, tables, scratch
-            cal.synchronize()
-            cal.profile_begin(every=1)
-            cal.gcc_phat_all_pairs_dev(d_one, cb, m, length, prm, d_tab)
-            cal.synchronize()
-            cal.profile_end()
-            alone = {k: v[0] for k, v in cal.profile_entries().items() if v[1] > 0}
-            # per FULL launch: the calibration frames end in a partial launch group, so the plain average per launch would
-            # mix a short launch in; total time / units processed x units of a full launch instead (pair kernels: pairs of a
-            # launch group; forward-spectrum kernels: the 256 frames of a launch of 128 packed transforms)
-            full_pairs = 2 * eng.pair_group_size(length)
-            for k, v in cal.profile_entries().items():
-                if v[1] <= 0:
-                    continue
-                forward = "k_pfa_fwd" in k or "FrameLoader" in k or "SpectrumStorer" in k
-                alone_avg[k] = v[0] / (cb * m) * min(256, cb * m) if forward else v[0] / (cb * pairs) * min(full_pairs, cb * pairs)
-            cal_pairs_per_launch = min(full_pairs, cb * pairs)
-        except Exception as exc:                                  # reported, never silent: the ranking falls back to elapsed totals
-            print(f"[bench] calibration frame failed ({exc}); ranking kernels by elapsed time", file=sys.stderr)
-            alone, alone_avg = {}, {}
-        finally:
-            if saved is None:
-                os.environ.pop("PAL_OVERLAP", None)
-            else:
-                os.environ["PAL_OVERLAP"] = saved
-            if cal is not None:
-                cal.close()
-    ranked = [k for k in sorted(alone, key=alone.get, reverse=True) if k in entries and entries[k][1] > 0]
-    dom = (ranked[0], entries[ranked[0]]) if ranked else (max(entries.items(), key=lambda kv: kv[1][0]) if entries else ("none", (0.0, 0)))
-    dom_name, (dom_ms, dom_launches) = dom
-    b_alg = algorithmic_bytes_per_pair(m, length)
-    chunk = eng.pair_group_size(length)
-    groups_per_step = -(-((b * pairs + 1) // 2) // chunk)
-    pairs_per_launch = b * pairs / groups_per_step
     info = eng.plan_info(length)
-    h_bins = length
-    # compulsory bytes of ONE pair inside each kernel class of the prime-factor / four-step pipelines (what that kernel
-    # must move for a pair even with perfect caching): spectra in, workspace out / in, correlation row out / in
-    n = info["n"]
-    spec_b, corr_b = 4 * h_bins * 8, n * 8                        # two half spectra in, one correlation row
-    y_b = n * 16 / 2                                              # prime-factor grid Y: one complex transform per two pairs
-    w_b = info["conv_len"] * 16 / 2                               # four-step workspace W per pair
-
-    def own(name):
-        if "k_pfa_cols_fin" in name: return y_b                   # the column pass that finishes its rows: Y in, 48-byte records out
-        if "k_pfa_cols" in name: return y_b + corr_b              # (also the fused k_pfa_cols_stats)
-        if "k_pfa_rows" in name: return spec_b + y_b
-        if "k_peak_stream" in name: return corr_b
-        if name.startswith("k_cols") and "_fwd" in name: return spec_b + w_b
-        if name.startswith("k_rows"): return 2 * w_b
-        if name.startswith("k_cols") and "_inv" in name: return w_b + corr_b
-        return None
-
-    achieved_job = value / world * b_alg / 1e9                     # per GPU
-    roofline = {"bound": "hbm", "achieved": round(achieved_job, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved_job / HBM_PEAK_GBS, 5),
-                "frac_is": "whole job per GPU: pairs/s x algorithmic bytes per pair / peak",
-                "algorithmic_bytes_per_pair": round(b_alg, 1), "traffic": None, "kernel": None}
-    if dom_launches:
-        live_s = dom_ms * 1e-3 / dom_launches
-        traffic, traffic_src = None, None
-        # counter passes are kept per configuration (tools/profile_round.sh): profiles/pmc_traffic.json for the metric run,
-        # profiles/pmc_traffic_<config>.json for C2 ... C5; a workload given by --mics / --length has none
-        tname = "pmc_traffic.json" if args.config == "metric" else f"pmc_traffic_{args.config}.json"
-        tpath = os.path.join(ROOT, "profiles", tname)
-        default_shape = not args.mics and not args.length
-        if os.path.exists(tpath) and default_shape:
+    kernels = alone_avg = chunk = roofline = roofline_fp64 = binding = parity = None
+    if args.full:
+        # ---- per-kernel durations: live (HIP events inside the timed region, three streams share the CUs) and alone
+        #      (one untimed calibration frame on a second, single-stream engine: PAL_OVERLAP=0, events around every launch)
+        entries = eng.profile_entries()
+        kernels = {k: {"ms": round(v[0], 3), "launches": v[1]} for k, v in entries.items() if v[1] > 0}
+        alone, alone_avg = {}, {}
+        cal_pairs_per_launch = 0.0
+        if rank == 0 and entries:
+            saved = os.environ.get("PAL_OVERLAP")
+            os.environ["PAL_OVERLAP"] = "0"
+            cal = None
             try:
-                traffic = traffic_lookup(json.load(open(tpath)), dom_name)
-                traffic_src = f"profiles/{tname} (rocprofv3 --pmc passes of an earlier run of this command, NOT this run)"
-            except Exception:
-                traffic = None
-        kb = own(dom_name)
-        roofline.update({
-            "traffic": traffic, "traffic_source": traffic_src, "kernel": dom_name,
-            "dominant_by": "largest time alone (single-stream calibration pass)" if ranked else "largest elapsed time",
-            "kernel_alone_launch_us": round(alone_avg[dom_name] * 1e3, 2) if dom_name in alone_avg else None,
-            "kernel_live_launch_us": round(live_s * 1e6, 2),
-            "kernel_live_note": "HIP events inside the timed region; three launch groups share the CUs, so this duration is stretched by concurrency",
-            "kernel_own_bytes_per_pair": kb,
-            "kernel_frac_alone": (round(kb * cal_pairs_per_launch / (alone_avg[dom_name] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-                                  if kb and dom_name in alone_avg else None),
-            "launches_timed": dom_launches, "event_sampling": f"every {args.event_every}th launch group",
-            "pairs_per_launch": round(pairs_per_launch, 2)})
-    flops = fp64_flops_per_pair(info, m, length)
-    flops_source = "operation count of the kernels' structure (DESIGN.md section 5), FMA = 2"
-    mpath = os.path.join(ROOT, "profiles", "fp64_flops_per_pair.json")
-    if not args.mics and not args.length and os.path.exists(mpath):
-        try:                                                       # measured instruction counts of an earlier PMC pass of this workload
-            rec = json.load(open(mpath))[args.config]
-            flops = float(rec["fp64_flops_per_pair"])
-            flops_source = "measured: fp64 instruction counters of an earlier PMC pass of this command, NOT this run (profiles/fp64_flops_per_pair.json)"
-        except Exception:
-            pass
-    roofline_fp64 = None
-    if flops:
-        tf = value / world * flops / 1e12
-        roofline_fp64 = {"bound": "fp64-valu", "achieved": round(tf, 2), "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(tf / FP64_PEAK_TFLOPS, 4), "flops_per_pair": round(flops),
-                         "peak_source": "v_fma_f64 rate measured on MI355X (tools/mfma_f64_rate.hip); data sheet 78.6",
-                         "flops_source": flops_source}
-    binding = None
-    if roofline_fp64:
-        binding = "fp64-valu" if roofline_fp64["frac"] > roofline["frac"] else "hbm"
+                cal = Engine(0 if share else local_rank)
+                cb = 1 if split_pairs else min(b, max(1, -(-2 * eng.pair_group_size(length) // pairs)))       # frames that fill one launch group
+                one = frames[:cb]
+                d_one, d_tab = cal.alloc(one.nbytes), cal.alloc(cb * pairs * RECORD.itemsize)
+                cal.upload(d_one, one)
+                cal.gcc_phat_all_pairs_dev(d_one, cb, m, length, prm, d_tab)      # plans, tables, scratch
+                cal.synchronize()
+                cal.profile_begin(every=1)
+                cal.gcc_phat_all_pairs_dev(d_one, cb, m, length, prm, d_tab)
+                cal.synchronize()
+                cal.profile_end()
+                alone = {k: v[0] for k, v in cal.profile_entries().items() if v[1] > 0}
+                # per FULL launch: the calibration frames end in a partial launch group, so the plain average per launch would
+                # mix a short launch in; total time / units processed x units of a full launch instead (pair kernels: pairs of a
+                # launch group; forward-spectrum kernels: the 256 frames of a launch of 128 packed transforms)
+                full_pairs = 2 * eng.pair_group_size(length)
+                for k, v in cal.profile_entries().items():
+                    if v[1] <= 0:
+                        continue
+                    forward = "k_pfa_fwd" in k or "FrameLoader" in k or "SpectrumStorer" in k
+                    alone_avg[k] = v[0] / (cb * m) * min(256, cb * m) if forward else v[0] / (cb * pairs) * min(full_pairs, cb * pairs)
+                cal_pairs_per_launch = min(full_pairs, cb * pairs)
+            except Exception as exc:                                  # reported, never silent: the ranking falls back to elapsed totals
+                print(f"[bench] calibration frame failed ({exc}); ranking kernels by elapsed time", file=sys.stderr)
+                alone, alone_avg = {}, {}
+            finally:
+                if saved is None:
+                    os.environ.pop("PAL_OVERLAP", None)
+                else:
+                    os.environ["PAL_OVERLAP"] = saved
+                if cal is not None:
+                    cal.close()
+        ranked = [k for k in sorted(alone, key=alone.get, reverse=True) if k in entries and entries[k][1] > 0]
+        dom = (ranked[0], entries[ranked[0]]) if ranked else (max(entries.items(), key=lambda kv: kv[1][0]) if entries else ("none", (0.0, 0)))
+        dom_name, (dom_ms, dom_launches) = dom
+        b_alg = algorithmic_bytes_per_pair(m, length)
+        chunk = eng.pair_group_size(length)
+        groups_per_step = -(-((b * pairs + 1) // 2) // chunk)
+        pairs_per_launch = b * pairs / groups_per_step
+        h_bins = length
+        # compulsory bytes of ONE pair inside each kernel class of the prime-factor / four-step pipelines (what that kernel
+        # must move for a pair even with perfect caching): spectra in, workspace out / in, correlation row out / in
+        n = info["n"]
+        spec_b, corr_b = 4 * h_bins * 8, n * 8                        # two half spectra in, one correlation row
+        y_b = n * 16 / 2                                              # prime-factor grid Y: one complex transform per two pairs
+        w_b = info["conv_len"] * 16 / 2                               # four-step workspace W per pair
 
-    # ---- parity sample against the CPU oracle's rows computed above ------------------------------------------------
-    parity = None
-    if want is not None and not split_pairs:
-        full = pair_list(m)
-        pick = np.flatnonzero((full[:, 0] < cm) & (full[:, 1] < cm))
-        got = host_table[0][pick]
-        parity = {"pairs_checked": int(pick.size), "k_sel_equal": int(np.count_nonzero(got["k_sel"] == want["k_sel"])),
-                  "branch_equal": int(np.count_nonzero(got["branch"] == want["branch"])),
-                  "max_rel_err_cmax": float(np.max(np.abs(got["cmax"] - want["cmax"]) / np.abs(want["cmax"])))}
+        def own(name):
+            if "k_pfa_cols_fin" in name: return y_b                   # the column pass that finishes its rows: Y in, 48-byte records out
+            if "k_pfa_cols" in name: return y_b + corr_b              # (also the fused k_pfa_cols_stats)
+            if "k_pfa_rows" in name: return spec_b + y_b
+            if "k_peak_stream" in name: return corr_b
+            if name.startswith("k_cols") and "_fwd" in name: return spec_b + w_b
+            if name.startswith("k_rows"): return 2 * w_b
+            if name.startswith("k_cols") and "_inv" in name: return w_b + corr_b
+            return None
+
+        achieved_job = value / world * b_alg / 1e9                     # per GPU
+        roofline = {"bound": "hbm", "achieved": round(achieved_job, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved_job / HBM_PEAK_GBS, 5),
+                    "frac_is": "whole job per GPU: pairs/s x algorithmic bytes per pair / peak",
+                    "algorithmic_bytes_per_pair": round(b_alg, 1), "traffic": None, "kernel": None}
+        if dom_launches:
+            live_s = dom_ms * 1e-3 / dom_launches
+            traffic, traffic_src = None, None
+            # counter passes are kept per configuration (tools/profile_round.sh): profiles/pmc_traffic.json for the metric run,
+            # profiles/pmc_traffic_<config>.json for C2 ... C5; a workload given by --mics / --length has none
+            tname = "pmc_traffic.json" if args.config == "metric" else f"pmc_traffic_{args.config}.json"
+            tpath = os.path.join(ROOT, "profiles", tname)
+            default_shape = not args.mics and not args.length
+            if os.path.exists(tpath) and default_shape:
+                try:
+                    traffic = traffic_lookup(json.load(open(tpath)), dom_name)
+                    traffic_src = f"profiles/{tname} (rocprofv3 --pmc passes of an earlier run of this command, NOT this run)"
+                except Exception:
+                    traffic = None
+            kb = own(dom_name)
+            roofline.update({
+                "traffic": traffic, "traffic_source": traffic_src, "kernel": dom_name,
+                "dominant_by": "largest time alone (single-stream calibration pass)" if ranked else "largest elapsed time",
+                "kernel_alone_launch_us": round(alone_avg[dom_name] * 1e3, 2) if dom_name in alone_avg else None,
+                "kernel_live_launch_us": round(live_s * 1e6, 2),
+                "kernel_live_note": "HIP events inside the timed region; three launch groups share the CUs, so this duration is stretched by concurrency",
+                "kernel_own_bytes_per_pair": kb,
+                "kernel_frac_alone": (round(kb * cal_pairs_per_launch / (alone_avg[dom_name] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+                                      if kb and dom_name in alone_avg else None),
+                "launches_timed": dom_launches, "event_sampling": f"every {args.event_every}th launch group",
+                "pairs_per_launch": round(pairs_per_launch, 2)})
+        flops = fp64_flops_per_pair(info, m, length)
+        flops_source = "operation count of the kernels' structure (DESIGN.md section 5), FMA = 2"
+        mpath = os.path.join(ROOT, "profiles", "fp64_flops_per_pair.json")
+        if not args.mics and not args.length and os.path.exists(mpath):
+            try:                                                       # measured instruction counts of an earlier PMC pass of this workload
+                rec = json.load(open(mpath))[args.config]
+                flops = float(rec["fp64_flops_per_pair"])
+                flops_source = "measured: fp64 instruction counters of an earlier PMC pass of this command, NOT this run (profiles/fp64_flops_per_pair.json)"
+            except Exception:
+                pass
+        roofline_fp64 = None
+        if flops:
+            tf = value / world * flops / 1e12
+            roofline_fp64 = {"bound": "fp64-valu", "achieved": round(tf, 2), "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(tf / FP64_PEAK_TFLOPS, 4), "flops_per_pair": round(flops),
+                             "peak_source": "v_fma_f64 rate measured on MI355X (tools/mfma_f64_rate.hip); data sheet 78.6",
+                             "flops_source": flops_source}
+        binding = None
+        if roofline_fp64:
+            binding = "fp64-valu" if roofline_fp64["frac"] > roofline["frac"] else "hbm"
+
+        # ---- parity sample against the CPU oracle's rows computed above ------------------------------------------------
+        parity = None
+        if want is not None and not split_pairs:
+            full = pair_list(m)
+            pick = np.flatnonzero((full[:, 0] < cm) & (full[:, 1] < cm))
+            got = host_table[0][pick]
+            parity = {"pairs_checked": int(pick.size), "k_sel_equal": int(np.count_nonzero(got["k_sel"] == want["k_sel"])),
+                      "branch_equal": int(np.count_nonzero(got["branch"] == want["branch"])),
+                      "max_rel_err_cmax": float(np.max(np.abs(got["cmax"] - want["cmax"]) / np.abs(want["cmax"])))}
 
     if rank == 0:
         if info.get("n1"):
@@ -512,7 +553,7 @@ def main() -> None:
                       else f"mic-pair GCC-PHAT correlations/s @{fs / 1000:g}kHz·{length / fs:g}s",
             "value": round(value, 1), "unit": "pair-correlations/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "strong" if split_pairs else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "scaling": "strong" if split_pairs else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": f"{cfg['label']}: {b} frame(s)/step/GPU x {m} mics x {length} samples @ {fs:g} Hz, "
                                    f"{pairs} pairs/frame, max_expected_delay={med}; {route}",
                        "name": args.config, "frames_per_step_per_gpu": b, "mics": m, "samples": length, "pairs_per_frame": pairs,
@@ -523,8 +564,9 @@ def main() -> None:
                                        else f"frames sharded over {world} GPU(s)")},
             "roofline": roofline, "roofline_fp64": roofline_fp64, "binding_roofline": binding,
             "cpu_baseline": cpu, "parity": parity, "kernels_ms": kernels,
-            "kernels_alone_us": {k: round(v * 1e3, 2) for k, v in alone_avg.items()},
-            "kernels_alone_note": "single-stream calibration pass, per full launch (group of 2 x %d pairs; forward kernels per 256 frames)" % chunk,
+            "kernels_alone_us": {k: round(v * 1e3, 2) for k, v in alone_avg.items()} if args.full else None,
+            "kernels_alone_note": ("single-stream calibration pass, per full launch (group of 2 x %d pairs; forward kernels per 256 frames)" % chunk
+                                   if args.full else None),
             "timed_region_s": round(elapsed, 3),
         }
         print(json.dumps(line), flush=True)

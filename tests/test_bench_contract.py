@@ -60,14 +60,14 @@ def _run_bench(args, queue):
 
 @pytest.mark.gpu
 def test_bench_line_keeps_the_contract():
-    """`python bench.py` (reduced frames / steps) prints ONE JSON line with every contract key, the roofline block and the
-    CPU baseline; the pairs it samples select the oracle's indices."""
+    """`python bench.py --full` (reduced frames / steps) prints ONE JSON line with every contract key, the roofline block and
+    the CPU baseline; the pairs it samples select the oracle's indices."""
     import multiprocessing as mp
     import conftest
     conftest.require_forkserver()
     ctx = mp.get_context("forkserver")          # started in conftest.pytest_sessionstart, before this process touched the GPU
     queue = ctx.Queue()
-    p = ctx.Process(target=_run_bench, args=(["--steps", "2", "--warmup", "1", "--frames", "2", "--cpu-mics", "6"], queue))
+    p = ctx.Process(target=_run_bench, args=(["--steps", "2", "--warmup", "1", "--frames", "2", "--cpu-mics", "6", "--full"], queue))
     p.start()
     rc, line, err = queue.get(timeout=900)
     p.join(timeout=60)
@@ -84,6 +84,67 @@ def test_bench_line_keeps_the_contract():
     assert cpu["kind"] == "port" and cpu["cores"] == 1 and cpu["value"] > 0 and "sample" in cpu
     assert d["parity"]["k_sel_equal"] == d["parity"]["pairs_checked"] == 15
     assert "workload" in d["config"] and "model" not in d["config"]
+    assert d["full"] is True and d["kernels_ms"] and d["roofline"]["kernel"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline keys with the --full blocks null;
+    --dump-outputs writes the last step's pair table, one float64 array per record field, whose selected indices are
+    the oracle's."""
+    import multiprocessing as mp
+    import conftest
+    from oracle import pal_oracle as O
+    from pyaudiolocalization_amd.synthetic import metric_frames
+    conftest.require_forkserver()
+    ctx = mp.get_context("forkserver")
+    queue = ctx.Queue()
+    out = tmp_path / "outputs"
+    p = ctx.Process(target=_run_bench, args=(["--steps", "3", "--warmup", "1", "--frames", "2", "--dump-outputs", str(out)], queue))
+    p.start()
+    rc, line, err = queue.get(timeout=900)
+    p.join(timeout=60)
+    assert rc == 0, err
+    d = json.loads(line)
+    assert CONTRACT <= set(d), sorted(CONTRACT - set(d))
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["value"] - 2 * 2016 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+    for key in ("roofline", "roofline_fp64", "cpu_baseline", "parity", "kernels_ms", "kernels_alone_us"):
+        assert d[key] is None, key
+    from pyaudiolocalization_amd import RECORD
+    got = {name: np.load(out / f"{name}.npy") for name in RECORD.names}
+    assert sorted(f.name for f in out.iterdir()) == sorted(f"{name}.npy" for name in RECORD.names)
+    for arr in got.values():
+        assert arr.dtype == np.float64 and arr.shape == (2, 2016)
+    want = O.all_pairs(metric_frames(1, 64, 44100)[0][:6], 44100.0, max_expected_delay=0.05)
+    full = np.array([(i, j) for i in range(64) for j in range(i + 1, 64)])
+    pick = np.flatnonzero((full[:, 0] < 6) & (full[:, 1] < 6))
+    assert np.array_equal(got["k_sel"][0][pick], want["k_sel"]) and np.array_equal(got["branch"][0][pick], want["branch"])
+    assert np.allclose(got["cmax"][0][pick], want["cmax"], rtol=1e-10, atol=1e-13)
+
+
+def test_dumped_outputs_are_capped_by_a_fixed_sample(tmp_path):
+    """dump_outputs: the whole table as float64 per field below the limit; above it a seeded sample of records that is the
+    same from run to run, with its flat indices, within the limit."""
+    import bench
+    from pyaudiolocalization_amd import RECORD
+    table = np.zeros((4, 7), dtype=RECORD)
+    table["k_sel"] = np.arange(28).reshape(4, 7)
+    table["cmax"] = np.linspace(0.0, 1.0, 28).reshape(4, 7)
+    bench.dump_outputs(str(tmp_path / "small"), table)
+    assert np.array_equal(np.load(tmp_path / "small" / "k_sel.npy"), table["k_sel"].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "small" / "cmax.npy"), table["cmax"])
+    big = np.zeros(100_000, dtype=RECORD)
+    big["k_sel"] = np.arange(big.size)
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), big, limit=1_000_000)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted([f"{n}.npy" for n in RECORD.names] + ["sample_index.npy"])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 1_000_000
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert np.all(np.diff(idx) > 0) and np.array_equal(np.load(tmp_path / "a" / "k_sel.npy"), idx)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
 
 
 def _run_bench_ranks(world, args, queue, env_extra):

@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for v in base "$@"; do
   if [ $v = base ]; then unset PAL_LIB_PATH; else export PAL_LIB_PATH=$ROOT/tools/bin/libpal_$v.so; fi
-  timeout -k 10 200 python3 $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench_$v.json 2> $OUT/bench_$v.err
+  timeout -k 10 200 python3 $ROOT/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench_$v.json 2> $OUT/bench_$v.err
   echo "== $v rc=$?"
   python3 -c "
 import json,sys

@@ -8,8 +8,8 @@ ROOT=$GRAFT_REPO_ROOT
 OUT=$ROOT/gpurun_out/${TAG}_l$L
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py --frames 16 --length $L --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats --output-format csv -- python3 $ROOT/bench.py --frames 16 --length $L --steps 4 --warmup 2 --no-cpu-baseline > $OUT/stats.log 2>&1; echo "stats rc=$?"
+python3 $ROOT/bench.py --frames 16 --length $L --steps 6 --warmup 2 --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats --output-format csv -- python3 $ROOT/bench.py --frames 16 --length $L --steps 4 --warmup 2 --full --no-cpu-baseline > $OUT/stats.log 2>&1; echo "stats rc=$?"
 PMC_CMD="python3 $ROOT/bench.py --frames 8 --length $L --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events"
 for pass in "fetch FETCH_SIZE" "write WRITE_SIZE"; do
   set -- $pass; name=$1; shift

@@ -17,8 +17,8 @@ cd /tmp && export TMPDIR=/tmp
 PARTS=${PARTS:-metric configs stream}
 CFGS=${CFGS:-c2 c3 c4 c5}
 if [[ " $PARTS " == *" metric "* ]]; then
-python3 $ROOT/bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats --output-format csv -- python3 $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/stats.log 2>&1; echo "stats rc=$?"
+python3 $ROOT/bench.py --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats --output-format csv -- python3 $ROOT/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $OUT/stats.log 2>&1; echo "stats rc=$?"
 PMC_CMD="python3 $ROOT/bench.py --steps 2 --warmup 1 --frames 16 --no-cpu-baseline --no-kernel-events"
 for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" "flops SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES" "sq SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_LDS"; do
   set -- $pass; name=$1; shift
@@ -29,8 +29,8 @@ python3 $ROOT/tools/flops_per_pair.py $OUT/pmc_flops.json $OUT/pmc_traffic.json 
 fi
 if [[ " $PARTS " == *" configs "* ]]; then
 for cfg in $CFGS; do
-  python3 $ROOT/bench.py --config $cfg --steps 10 --warmup 3 > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err; echo "bench $cfg rc=$?"
-  rocprofv3 --kernel-trace --stats -d $OUT/stats_$cfg -o stats --output-format csv -- python3 $ROOT/bench.py --config $cfg --steps 4 --warmup 2 --no-cpu-baseline > $OUT/stats_$cfg.log 2>&1
+  python3 $ROOT/bench.py --config $cfg --steps 10 --warmup 3 --full > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err; echo "bench $cfg rc=$?"
+  rocprofv3 --kernel-trace --stats -d $OUT/stats_$cfg -o stats --output-format csv -- python3 $ROOT/bench.py --config $cfg --steps 4 --warmup 2 --full --no-cpu-baseline > $OUT/stats_$cfg.log 2>&1
   # memory-side traffic and fp64 operations of the configuration's kernels: the same three counter passes as the metric run
   CFG_CMD="python3 $ROOT/bench.py --config $cfg --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-events"
   for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" "flops SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU SQ_WAVES"; do

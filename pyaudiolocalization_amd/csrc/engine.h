@@ -95,8 +95,8 @@ struct Engine {
   int fin_dense = -1;              // PAL_FIN_DENSE: 1 / 0 = the pass on every / no dense column DFT; -1 (unset): where it measured faster
   bool fin_strips = false;         // PAL_FIN_STRIPS=1: also on short columns beside 16384-point row tiles
   bool fin_four = false;           // PAL_FIN_FOUR=1: on the four-step last pass
-  bool fin_wide = false;           // PAL_FIN_WIDE=1: on column DFTs of five or six chunks
   bool fin_hist = false;           // PAL_FIN_HIST=1: histogram windows for every threshold multiplier
+  bool nohist(const pal_phat_params& prm) const;   // the threshold needs no histograms: 'adaptive', or 'median' with a multiplier in 0 .. 2
   bool rows_lean = true;           // PAL_ROWS_LEAN=0: stored rows of the other routes keep the three statistics launches
   long long rows_lean_min = 200000;   // PAL_ROWS_LEAN_MIN=<pairs>: smallest call that takes k_rows_lean (tests lower it)
   bool lean_store = true;          // PAL_LEAN_STORE=0: stored rows keep the round-2 statistics (pfa_cols_stats.h / three launches) + k_peak_finish

@@ -330,8 +330,6 @@ int pal_create(int device, pal_handle* out) {
   e->fin_strips = getenv("PAL_FIN_STRIPS") != nullptr;
   env = getenv("PAL_FIN_FOUR");
   e->fin_four = env && atoi(env) != 0;
-  env = getenv("PAL_FIN_WIDE");
-  e->fin_wide = env && atoi(env) != 0;
   e->fin_hist = getenv("PAL_FIN_HIST") != nullptr;
   env = getenv("PAL_ROWS_LEAN");
   if (env) e->rows_lean = atoi(env) != 0;

@@ -390,14 +390,15 @@ bool Engine::pfa_can_finish(const Plan& pl, const pal_phat_params& prm) const {
   if (!f.r89 && nblk < 12) cols_ok = false;
   if (fin_dense >= 0) cols_ok = f.r89 != nullptr || fin_dense != 0;      // PAL_FIN_DENSE=1 / 0: every / no dense column DFT
   if (f.nch <= 1 && strips) cols_ok = true;
-  // five and six chunks (N1 up to 133: C5's 103 x 233; five- / six-wavefront blocks, no histogram form): opt-in, PAL_FIN_WIDE=1.
-  // Correct, but C5 runs 2.53 against 2.58 M pairs/s with it: 960 blocks are one round of the machine, every wavefront is in the
-  // same phase at the same time and the pass (160 us) is the sum of its latencies, where the separate launches (70 + 18 + 31 + 32) overlap
-  const bool nohist = prm.threshold_method > 0 || (prm.threshold_multiplier >= 0 && prm.threshold_multiplier <= 2.0 && !fin_hist);
-  if (f.nch >= 5) {
-    return fin_cols && fin_wide && fuse_peaks && f.on() && f.nch <= 6 && nohist && prm.num_peaks == 1 && f.n2 >= 124;
-  }
+  // (five and six chunks, N1 up to 133, are not finished here whatever the switches: pfa_can_fuse stops at four.  Tried with five- /
+  // six-wavefront blocks: correct, but C5 ran 2.53 against 2.58 M pairs/s with it - 960 blocks are one round of the machine, every
+  // wavefront is in the same phase at the same time and the pass (160 us) is the sum of its latencies, where the separate launches
+  // (70 + 18 + 31 + 32) overlap.  Their stored rows take k_rows_lean)
   return fin_cols && pfa_can_fuse(pl) && prm.num_peaks == 1 && f.n2 >= 256 && cols_ok;
+}
+
+bool Engine::nohist(const pal_phat_params& prm) const {
+  return prm.threshold_method > 0 || (prm.threshold_multiplier >= 0 && prm.threshold_multiplier <= 2.0 && !fin_hist);
 }
 
 // The blocks of a finishing pass wait for their siblings (pfa_cols_fin.h).  ONE such launch is deadlock-free (its workgroups are
@@ -475,8 +476,7 @@ int Engine::fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, int gri
       fa.win_hi = int(hi > n - 2 ? n - 2 : hi);
     }
   }
-  const bool no_cheb = fin_hist;                               // diagnostics: histograms for every multiplier
-  fa.cheb = a.method == 0 && prm.threshold_multiplier >= 0 && prm.threshold_multiplier <= 2.0 && !no_cheb ? 1 : 0;
+  fa.cheb = a.method == 0 && nohist(prm) ? 1 : 0;
   fa.stamps = nullptr;
   static const bool want_stamps = getenv("PAL_DEBUG_STAMPS") != nullptr;
   nwg = 8u * unsigned((G + 7) / 8) * unsigned(nblk);
@@ -494,8 +494,7 @@ int Engine::fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, int gri
 bool Engine::fourstep_can_finish(const Plan& pl, const pal_phat_params& prm) const {
   const Conv& c = pl.inv;
   const bool off = !fin_four;                                  // opt-in (PAL_FIN_FOUR=1): measured 0.36 against 0.50 M pairs/s for the stored rows + statistics launches
-  const bool nohist = prm.threshold_method > 0 || (prm.threshold_multiplier >= 0 && prm.threshold_multiplier <= 2.0 && !fin_hist);
-  return fin_cols && !off && c.reg && c.M1() <= 24 && prm.num_peaks == 1 && nohist && pl.nout == pl.n;
+  return fin_cols && !off && c.reg && c.M1() <= 24 && prm.num_peaks == 1 && nohist(prm) && pl.nout == pl.n;
 }
 
 int Engine::fourstep_pair_group_fin(const Plan& pl, const cd* W, int G, int rows, const int* zero_rows, const pal_phat_params& prm, int n2,
@@ -525,10 +524,9 @@ int Engine::fourstep_pair_group_fin(const Plan& pl, const cd* W, int G, int rows
 // Statistics of rows that are already in HBM, any route (k_rows_lean): one launch instead of pivots + stream + finish where one peak per
 // row is asked for and the threshold needs no histograms; flagged rows are resolved at the end of the call.
 bool Engine::rows_can_lean(const Plan& pl, const pal_phat_params& prm) const {
-  const bool nohist = prm.threshold_method > 0 || (prm.threshold_multiplier >= 0 && prm.threshold_multiplier <= 2.0 && !fin_hist);
   // Measured: rows of 12 013 ... 24 013 samples +2 ... +8 % (C5 2.58 -> 2.87 M pairs/s: 66 us per group against 18 + 31 + 32), rows of
   // 88 201 ... 88 367 -3 ... +1 %, C4's 191 999 the same: long rows keep the three launches (their stream pass runs at the HBM rate)
-  return rows_lean && fin_cols && prm.num_peaks == 1 && nohist && pl.nout == pl.n && pl.n >= 4096 && pl.n <= 50000;
+  return rows_lean && fin_cols && prm.num_peaks == 1 && nohist(prm) && pl.nout == pl.n && pl.n >= 4096 && pl.n <= 50000;
 }
 
 int Engine::rows_lean_group(const Plan& pl, const double* corr, size_t stride, int G, int rows, const pal_phat_params& prm, int n2,
@@ -556,19 +554,19 @@ int Engine::rows_lean_group(const Plan& pl, const double* corr, size_t stride, i
 // peak per row is asked for and the threshold needs no histograms.
 bool Engine::pfa_can_lean_store(const Plan& pl, const pal_phat_params& prm) const {
   const Pfa& f = pl.pfa;
-  const bool nohist = prm.threshold_method > 0 || (prm.threshold_multiplier >= 0 && prm.threshold_multiplier <= 2.0 && !fin_hist);
   // Several rounds of column blocks per launch group, or the pass is the sum of one block's latencies: C5 (103 x 233: four blocks per
   // transform, 960 per group, one round) measured 2.32 against 2.60 M pairs/s with it; C3 (7 x 6857: 28 blocks) 1.16 against 1.08,
   // C2 (17 x 5647: 23 blocks) 0.422 against 0.417
   const int nblk = (f.n2 + (f.nch <= 1 ? 4 : 1) * kColsOwn - 1) / ((f.nch <= 1 ? 4 : 1) * kColsOwn);
   // (five and six chunks, N1 = 91 ... 127 beside 700 - 970 columns: 0.63 - 0.66 against 0.69 - 0.71 M with it: they keep the three statistics launches)
-  return lean_store && fin_cols && fuse_peaks && f.on() && f.nch >= 1 && f.nch <= 4 && nblk >= 12 && prm.num_peaks == 1 && nohist;
+  return lean_store && fin_cols && fuse_peaks && f.on() && f.nch >= 1 && f.nch <= 4 && nblk >= 12 && prm.num_peaks == 1 && nohist(prm);
 }
 
 int Engine::pfa_pair_group_fin(const Plan& pl, const cd* permuted, const int4* quads, int G, int rows, cd* Y, const int* zero_rows,
                                const pal_phat_params& prm, int n2, pal_pair_record* table, int* need, int slot, hipStream_t on,
                                double* corr, size_t stride) {
   const Pfa& f = pl.pfa;
+  if (f.nch > 4) return fail(PAL_ERR_INTERNAL, "finishing column pass with %d chunks", f.nch);   // (pfa_can_finish never asks for it)
   const bool shortcols = f.nch <= 1;                           // short column DFTs (N1 <= 23): the four wavefronts of a block are four strips
   const int nblk = (f.n2 + (shortcols ? 4 : 1) * kColsOwn - 1) / ((shortcols ? 4 : 1) * kColsOwn);
   PeakArgs a;
@@ -586,27 +584,18 @@ int Engine::pfa_pair_group_fin(const Plan& pl, const cd* permuted, const int4* q
     const bool full = (f.n1 - 1) / 2 == f.nch * kPfaTC;
     // histograms only where the bound sqrt(2 mean(x^2)) on the median cannot decide: multipliers above 2 (or negative)
     const bool hist = !(a.method > 0 || fa.cheb);
-    const int nw = f.nch == 2 ? 2 : (f.nch == 3 && !hist ? 3 : (f.nch >= 5 ? f.nch : 4));   // (three chunks: three wavefronts where the statistics are per wavefront)
-    if (f.nch >= 5 && hist) return fail(PAL_ERR_INTERNAL, "finishing column pass with %d chunks and histograms", f.nch);
+    const int nw = f.nch == 2 ? 2 : (f.nch == 3 && !hist ? 3 : 4);   // (three chunks: three wavefronts where the statistics are per wavefront)
     FinSrc src{Y, f.T, static_cast<const Rader89Tab*>(f.r89), nullptr, nullptr, nullptr};
     PAL_TRY(fin_serialize(on));
 #define PAL_COLS_FIN(MODE, HI, FU, NW) k_pfa_cols_fin<MODE, kPfaTC, kPfaUnr, HI, FU, NW><<<grid, dim3(64 * NW), 0, on>>>(src, f.n1, f.n2, G, f.nch, nblk, zero_rows, a, fa, rows)
+#define PAL_COLS_FIN_FU(MODE, HI, NW) do { if (full) PAL_COLS_FIN(MODE, HI, true, NW); else PAL_COLS_FIN(MODE, HI, false, NW); } while (0)
     if (!hist) fa.pw = shortcols ? 4 : nw;                    // one FinPartial / `done` word per wavefront (pfa_fin_lean.h)
     if (shortcols) { if (hist) PAL_COLS_FIN(kColsStrips, true, false, 4); else PAL_COLS_FIN(kColsStrips, false, false, 4); }
     else if (f.r89 && full && nw == 4) { if (hist) PAL_COLS_FIN(kColsRader89, true, true, 4); else PAL_COLS_FIN(kColsRader89, false, true, 4); }
-    else if (nw == 2) {
-      if (hist) { if (full) PAL_COLS_FIN(kColsDense, true, true, 2); else PAL_COLS_FIN(kColsDense, true, false, 2); }
-      else { if (full) PAL_COLS_FIN(kColsDense, false, true, 2); else PAL_COLS_FIN(kColsDense, false, false, 2); }
-    } else if (nw == 3) {
-      if (full) PAL_COLS_FIN(kColsDense, false, true, 3); else PAL_COLS_FIN(kColsDense, false, false, 3);
-    } else if (nw == 5) {
-      if (full) PAL_COLS_FIN(kColsDense, false, true, 5); else PAL_COLS_FIN(kColsDense, false, false, 5);
-    } else if (nw == 6) {
-      if (full) PAL_COLS_FIN(kColsDense, false, true, 6); else PAL_COLS_FIN(kColsDense, false, false, 6);
-    } else {
-      if (hist) { if (full) PAL_COLS_FIN(kColsDense, true, true, 4); else PAL_COLS_FIN(kColsDense, true, false, 4); }
-      else { if (full) PAL_COLS_FIN(kColsDense, false, true, 4); else PAL_COLS_FIN(kColsDense, false, false, 4); }
-    }
+    else if (nw == 3) PAL_COLS_FIN_FU(kColsDense, false, 3);  // (per-wavefront statistics only)
+    else if (nw == 2) { if (hist) PAL_COLS_FIN_FU(kColsDense, true, 2); else PAL_COLS_FIN_FU(kColsDense, false, 2); }
+    else { if (hist) PAL_COLS_FIN_FU(kColsDense, true, 4); else PAL_COLS_FIN_FU(kColsDense, false, 4); }
+#undef PAL_COLS_FIN_FU
 #undef PAL_COLS_FIN
     PAL_HIP(hipGetLastError());
     PAL_TRY(fin_done(on));

@@ -70,7 +70,7 @@ struct FinArgs {
   double* corr;                   // null, or [rows][stride]: the pass ALSO stores the correlation rows (the caller wants them, or the plan
   size_t stride;                  //   has no finishing form): nobody polls siblings then, the finisher reads the SNR window from the stored row
   int store_rows;                 // 1: this pass writes the rows (column forms); 0 with corr set: they are there already (k_rows_lean reads them)
-  int cheb;                       // 1: no histograms - the median of |corr| is bounded by sqrt(2 mean(corr^2)) (see fin_row)
+  int cheb;                       // 1: no histograms - the median of |corr| is bounded by sqrt(2 mean(corr^2)) (see fin_decide)
   unsigned long long* stamps;     // diagnostics (PAL_DEBUG_STAMPS=1): [workgroup][8] 100 MHz clock reads of lane 0 per phase
 };
 
@@ -141,40 +141,141 @@ constexpr double kEpochUnit = 4294967296.0;                    // 2^32: an entry
 // the waiting blocks give up after a few milliseconds, leave, and the late siblings find the maxima they need.
 constexpr int kSpinLimit = 1 << 11;
 
+// ---- the finisher's view of one row: per lane while it gathers, uniform once the caller has merged it across its lanes
+struct FinRow {
+  double vmax = 0, vmin = INFINITY, hb = 0, plat = -INFINITY, s1 = 0, s2 = 0, a1 = 0, w1 = 0, w2 = 0;
+  int imax = -1, mb = -1;
+  double hw = 0, hm = 0, platw = -INFINITY;
+  int mw = -1, mm = -1;
+  bool abandoned = false;                                      // a block gave up waiting for the row's argmax: its window sums are missing
+};
+
+// ---- the selection of ONE peak from a row's merged statistics (uniform in every calling lane), for the block finisher (fin_row) and
+//      the wavefront finisher (pfa_fin_lean.h fin_row_wave): plateau flags, SNR, primary threshold, the fallback chain, and the
+//      record or the row's `need` flag, written by the lane with `writer` set.  `flag` / `why` carry what the caller flagged already
+//      (s.imax is valid then); with `interval` the caller hands in the median's threshold interval [tlo, thi] (histogram windows)
+__device__ __forceinline__ void fin_decide(const PeakArgs& pa, const FinArgs& fa, int row, const FinRow& s, bool flag, int why, bool interval,
+                                           double tlo, double thi, bool writer) {
+  const int n = pa.n;
+  const bool windowed = fa.windowed != 0;
+  const int imax = s.imax;
+  const double vmax = s.vmax, hb = s.hb, hw = s.hw, hm = s.hm;
+  const int mb = s.mb, mw = s.mw, mm = s.mm;
+  // a tie that may outrank the best strict peak (plateaus are resolved from the stored row)
+  if (s.plat > -INFINITY && (mb < 0 || s.plat >= hb)) { flag = true; why |= 2; }
+  if (windowed && s.platw > -INFINITY && (mw < 0 || s.platw >= hw)) { flag = true; why |= 4; }
+
+  // ---- SNR (utils.py:238-250): totals minus the window around the maximum
+  const int wlo_s = imax - pa.snr_w > 0 ? imax - pa.snr_w : 0;
+  const int whi_s = imax + pa.snr_w < n ? imax + pa.snr_w : n;
+  const double nn = double(n - (whi_s - wlo_s));
+  const double o1 = s.s1 - s.w1, o2 = s.s2 - s.w2;
+  if (!(o2 >= 0.25 * s.s2)) { flag = true; why |= 8; }         // the window holds most of the energy: two-pass sum of the noise region
+  double var = (o2 - o1 * o1 / nn) / nn;
+  if (var < 0) var = 0;
+  const double noise = sqrt(var);
+  const double snr = noise == 0.0 ? INFINITY : vmax / noise;
+
+  // ---- primary threshold (utils.py:144-149): exact ('adaptive'), the caller's interval, or a bound on the median
+  if (pa.method != 0) {
+    double va = (s.s2 - s.a1 * s.a1 / double(n)) / double(n);
+    if (va < 0) va = 0;
+    tlo = thi = pa.mult * (s.a1 / double(n) + sqrt(va));       // utils.py:147
+  } else if (!interval) {
+    // No histograms: at most half of the samples can have x^2 >= 2 mean(x^2) (Markov), so median(|corr|) <= sqrt(2 s2 / n).
+    // A peak at or above mult x that bound passes the threshold of utils.py:145 for certain - and the highest peak of a PHAT
+    // row stands 3 to 4 sigma above a median of 0.67 sigma, the bound is 1.41 sigma.  A candidate below the bound is not
+    // decided here: the row is flagged and the stored-row path computes its exact median.
+    thi = pa.mult * sqrt(2.0 * s.s2 / double(n)) * (1.0 + 1e-12);
+    tlo = -INFINITY;
+  }
+
+  // ---- the fallback chain of utils.py:152-179 for ONE peak
+  const double mean_abs = s.a1 / double(n);
+  int branch = 0, sel = imax;
+  double sel_h = vmax;
+  bool argmax_fallback = false;
+  if (!flag) {
+    bool alt = false;
+    if (mb >= 0 && hb >= thi) {
+    } else if (mb >= 0 && hb >= tlo) {
+      flag = true;                                             // inside the median's interval
+      why |= 32;
+    } else {
+      branch |= PAL_BR_ALT_THRESHOLD;
+      alt = true;
+      if (!(mb >= 0 && hb >= mean_abs)) { branch |= PAL_BR_ARGMAX_NO_PEAKS; argmax_fallback = true; }
+    }
+    if (!flag && !argmax_fallback) {
+      if (!windowed) {
+        sel = mb; sel_h = hb;                                  // the highest peak of the row is kept by the distance rule
+      } else {
+        const double t_lo = alt ? mean_abs : tlo, t_hi = alt ? mean_abs : thi;
+        bool found = false;
+        if (mw >= 0 && hw >= t_hi) found = true;
+        else if (mw >= 0 && hw >= t_lo) { flag = true; why |= 64; }
+        if (!flag && !found) {                                 // no peak of the first search inside the window: mean(|corr|), then argmax
+          branch |= PAL_BR_WINDOW_RETRY;
+          if (mw >= 0 && hw >= mean_abs) found = true;
+          else { branch |= PAL_BR_ARGMAX_WINDOW; argmax_fallback = true; }
+        }
+        if (found) {
+          // the window's best peak is kept unless a HIGHER peak lies closer than `distance`; inside the window there is none,
+          // and a sample outside it is that close only to peaks within distance - 2 of the window's edge.  The margins' best
+          // peak stands for every peak there: only if IT is higher can the window's peak be suppressed (whether it is - the
+          // margin peak may be suppressed itself - is a chain the stored row resolves)
+          const bool near = mw - fa.win_lo < pa.dist - 1 || fa.win_hi - mw < pa.dist - 1;
+          if (near && mm >= 0 && higher(hm, mm, hw, mw)) { flag = true; why |= 128; }
+          else { sel = mw; sel_h = hw; }
+        }
+      }
+    }
+    if (argmax_fallback) { sel = imax; sel_h = vmax; }
+  }
+  if (writer) {
+    fa.need[row] = flag ? 1 : 0;
+    if (flag) {
+      atomicAdd(fa.status + 4, 1);
+      for (int b = 0; b < 8; ++b)
+        if (why >> b & 1) atomicAdd(fa.status + 5 + b, 1);
+    } else {
+      pal_pair_record r;
+      r.k_sel = sel; r.branch = branch; r.k_argmax = imax; r.n_sel = 1;
+      r.cmax = vmax; r.cmin = s.vmin; r.snr = snr; r.sel_height = sel_h;
+      fa.table[row] = r;
+    }
+  }
+}
+
 // ---- the finishing block: one row from the blocks' published results (all LANES lanes, uniform control flow) ----
 template <int LANES>
 __device__ __forceinline__ void fin_row(const PeakArgs& pa, const FinArgs& fa, int row, int N1, int N2, int nch, FinShared& fs, int tid) {
   constexpr int NW = LANES / 64;
   const int S = pa.splits, n = pa.n;
   const bool windowed = fa.windowed != 0;
-  const bool want_median = pa.method == 0;
   // ---- every lane: some wavefronts' maxima, at most a few blocks' results and edge samples; merged locally, then across the workgroup
-  double vmax = 0, vmin = INFINITY, hb = 0, plat = -INFINITY, s1 = 0, s2 = 0, a1 = 0, w1 = 0, w2 = 0;
-  int imax = -1, mb = -1;
-  double hw = 0, hm = 0, platw = -INFINITY;
-  int mw = -1, mm = -1;
-  bool abandoned = false;                                      // a block gave up waiting for the row's argmax: its window sums are missing
+  FinRow s;
   {
     const double* em = fa.emax + size_t(row) * S * 8;
     for (int q = tid; q < S * 4; q += LANES) {
       if ((q & 3) >= nch) continue;
       const double v = ld_agent(em + 2 * q);
       const int i = int(ld_agent(em + 2 * q + 1) - double(fa.epoch) * kEpochUnit) - 1;      // (complete: every block of the transform is done)
-      if (i >= 0 && i < n && (imax < 0 || arg_better<0>(v, i, vmax, imax))) { vmax = v; imax = i; }
+      if (i >= 0 && i < n && (s.imax < 0 || arg_better<0>(v, i, s.vmax, s.imax))) { s.vmax = v; s.imax = i; }
     }
   }
   for (int q = tid; q < S * fa.pw; q += LANES) {
     const FinPartial pt = ld_words(fa.parts + size_t(row) * S * fa.pw + q);
-    vmin = fmin(vmin, pt.vmin);
-    if (pt.mb >= 0 && (mb < 0 || higher(pt.hb, pt.mb, hb, mb))) { hb = pt.hb; mb = pt.mb; }
-    plat = fmax(plat, pt.plat);
-    s1 += pt.s1; s2 += pt.s2; a1 += pt.a1;
-    w1 += pt.w1; w2 += pt.w2;
-    abandoned = abandoned || pt.pad != 0;
+    s.vmin = fmin(s.vmin, pt.vmin);
+    if (pt.mb >= 0 && (s.mb < 0 || higher(pt.hb, pt.mb, s.hb, s.mb))) { s.hb = pt.hb; s.mb = pt.mb; }
+    s.plat = fmax(s.plat, pt.plat);
+    s.s1 += pt.s1; s.s2 += pt.s2; s.a1 += pt.a1;
+    s.w1 += pt.w1; s.w2 += pt.w2;
+    s.abandoned = s.abandoned || pt.pad != 0;
     if (windowed) {
-      if (pt.mw >= 0 && (mw < 0 || higher(pt.hw, pt.mw, hw, mw))) { hw = pt.hw; mw = pt.mw; }
-      if (pt.mm >= 0 && (mm < 0 || higher(pt.hm, pt.mm, hm, mm))) { hm = pt.hm; mm = pt.mm; }
-      platw = fmax(platw, pt.platw);
+      if (pt.mw >= 0 && (s.mw < 0 || higher(pt.hw, pt.mw, s.hw, s.mw))) { s.hw = pt.hw; s.mw = pt.mw; }
+      if (pt.mm >= 0 && (s.mm < 0 || higher(pt.hm, pt.mm, s.hm, s.mm))) { s.hm = pt.hm; s.mm = pt.mm; }
+      s.platw = fmax(s.platw, pt.platw);
     }
   }
   // the grid's first and last column: neighbours in another output index (m - 1 = (N2 - 1, t - 1), m + 1 = (0, t + 1))
@@ -191,87 +292,65 @@ __device__ __forceinline__ void fin_row(const PeakArgs& pa, const FinArgs& fa, i
     const bool pk = xl < x && xr < x;
     const bool inw = windowed && m >= fa.win_lo && m <= fa.win_hi;
     const bool inm = windowed && !inw && m >= fa.win_lo - (pa.dist - 1) && m <= fa.win_hi + (pa.dist - 1);
-    if (tie) plat = fmax(plat, x);
-    if (tie && (inw || inm)) platw = fmax(platw, x);
-    if (pk && (mb < 0 || higher(x, m, hb, mb))) { hb = x; mb = m; }
-    if (pk && inw && (mw < 0 || higher(x, m, hw, mw))) { hw = x; mw = m; }
-    if (pk && inm && (mm < 0 || higher(x, m, hm, mm))) { hm = x; mm = m; }
+    if (tie) s.plat = fmax(s.plat, x);
+    if (tie && (inw || inm)) s.platw = fmax(s.platw, x);
+    if (pk && (s.mb < 0 || higher(x, m, s.hb, s.mb))) { s.hb = x; s.mb = m; }
+    if (pk && inw && (s.mw < 0 || higher(x, m, s.hw, s.mw))) { s.hw = x; s.mw = m; }
+    if (pk && inm && (s.mm < 0 || higher(x, m, s.hm, s.mm))) { s.hm = x; s.mm = m; }
   }
   {
-    double nvmin = -vmin;
+    double nvmin = -s.vmin;
     for (int o = 32; o > 0; o >>= 1) {
-      const double ov = shfl_down_d(vmax, o);
-      const int oi = __shfl_down(imax, o, 64);
-      if (oi >= 0 && (imax < 0 || arg_better<0>(ov, oi, vmax, imax))) { vmax = ov; imax = oi; }
-      const double hv = shfl_down_d(hb, o);
-      const int hi_ = __shfl_down(mb, o, 64);
-      if (hi_ >= 0 && (mb < 0 || higher(hv, hi_, hb, mb))) { hb = hv; mb = hi_; }
-      const double wv = shfl_down_d(hw, o);
-      const int wi = __shfl_down(mw, o, 64);
-      if (wi >= 0 && (mw < 0 || higher(wv, wi, hw, mw))) { hw = wv; mw = wi; }
-      const double gv = shfl_down_d(hm, o);
-      const int gi = __shfl_down(mm, o, 64);
-      if (gi >= 0 && (mm < 0 || higher(gv, gi, hm, mm))) { hm = gv; mm = gi; }
-      plat = fmax(plat, shfl_down_d(plat, o));
-      platw = fmax(platw, shfl_down_d(platw, o));
+      const double ov = shfl_down_d(s.vmax, o);
+      const int oi = __shfl_down(s.imax, o, 64);
+      if (oi >= 0 && (s.imax < 0 || arg_better<0>(ov, oi, s.vmax, s.imax))) { s.vmax = ov; s.imax = oi; }
+      const double hv = shfl_down_d(s.hb, o);
+      const int hi_ = __shfl_down(s.mb, o, 64);
+      if (hi_ >= 0 && (s.mb < 0 || higher(hv, hi_, s.hb, s.mb))) { s.hb = hv; s.mb = hi_; }
+      const double wv = shfl_down_d(s.hw, o);
+      const int wi = __shfl_down(s.mw, o, 64);
+      if (wi >= 0 && (s.mw < 0 || higher(wv, wi, s.hw, s.mw))) { s.hw = wv; s.mw = wi; }
+      const double gv = shfl_down_d(s.hm, o);
+      const int gi = __shfl_down(s.mm, o, 64);
+      if (gi >= 0 && (s.mm < 0 || higher(gv, gi, s.hm, s.mm))) { s.hm = gv; s.mm = gi; }
+      s.plat = fmax(s.plat, shfl_down_d(s.plat, o));
+      s.platw = fmax(s.platw, shfl_down_d(s.platw, o));
       nvmin = fmax(nvmin, shfl_down_d(nvmin, o));
-      s1 += shfl_down_d(s1, o); s2 += shfl_down_d(s2, o); a1 += shfl_down_d(a1, o);
-      w1 += shfl_down_d(w1, o); w2 += shfl_down_d(w2, o);
+      s.s1 += shfl_down_d(s.s1, o); s.s2 += shfl_down_d(s.s2, o); s.a1 += shfl_down_d(s.a1, o);
+      s.w1 += shfl_down_d(s.w1, o); s.w2 += shfl_down_d(s.w2, o);
     }
     __syncthreads();                                           // (the previous row's readers are done with the scratch)
     if ((tid & 63) == 0) {
       FinWave& w = fs.wave[tid >> 6];
-      w.vmax = vmax; w.imax = imax; w.hb = hb; w.mb = mb; w.hw = hw; w.mw = mw; w.hm = hm; w.mm = mm; w.plat = plat; w.platw = platw; w.nvmin = nvmin;
-      w.s1 = s1; w.s2 = s2; w.a1 = a1; w.w1 = w1; w.w2 = w2;
+      w.vmax = s.vmax; w.imax = s.imax; w.hb = s.hb; w.mb = s.mb; w.hw = s.hw; w.mw = s.mw; w.hm = s.hm; w.mm = s.mm;
+      w.plat = s.plat; w.platw = s.platw; w.nvmin = nvmin;
+      w.s1 = s.s1; w.s2 = s.s2; w.a1 = s.a1; w.w1 = s.w1; w.w2 = s.w2;
     }
     __syncthreads();
     const FinWave w0 = fs.wave[0];
-    vmax = w0.vmax; imax = w0.imax; hb = w0.hb; mb = w0.mb; hw = w0.hw; mw = w0.mw; hm = w0.hm; mm = w0.mm; plat = w0.plat; platw = w0.platw; nvmin = w0.nvmin;
-    s1 = w0.s1; s2 = w0.s2; a1 = w0.a1; w1 = w0.w1; w2 = w0.w2;
+    s.vmax = w0.vmax; s.imax = w0.imax; s.hb = w0.hb; s.mb = w0.mb; s.hw = w0.hw; s.mw = w0.mw; s.hm = w0.hm; s.mm = w0.mm;
+    s.plat = w0.plat; s.platw = w0.platw; nvmin = w0.nvmin;
+    s.s1 = w0.s1; s.s2 = w0.s2; s.a1 = w0.a1; s.w1 = w0.w1; s.w2 = w0.w2;
     for (int k = 1; k < NW; ++k) {
       const FinWave w = fs.wave[k];
-      if (w.imax >= 0 && (imax < 0 || arg_better<0>(w.vmax, w.imax, vmax, imax))) { vmax = w.vmax; imax = w.imax; }
-      if (w.mb >= 0 && (mb < 0 || higher(w.hb, w.mb, hb, mb))) { hb = w.hb; mb = w.mb; }
-      if (w.mw >= 0 && (mw < 0 || higher(w.hw, w.mw, hw, mw))) { hw = w.hw; mw = w.mw; }
-      if (w.mm >= 0 && (mm < 0 || higher(w.hm, w.mm, hm, mm))) { hm = w.hm; mm = w.mm; }
-      plat = fmax(plat, w.plat); platw = fmax(platw, w.platw); nvmin = fmax(nvmin, w.nvmin);
-      s1 += w.s1; s2 += w.s2; a1 += w.a1; w1 += w.w1; w2 += w.w2;
+      if (w.imax >= 0 && (s.imax < 0 || arg_better<0>(w.vmax, w.imax, s.vmax, s.imax))) { s.vmax = w.vmax; s.imax = w.imax; }
+      if (w.mb >= 0 && (s.mb < 0 || higher(w.hb, w.mb, s.hb, s.mb))) { s.hb = w.hb; s.mb = w.mb; }
+      if (w.mw >= 0 && (s.mw < 0 || higher(w.hw, w.mw, s.hw, s.mw))) { s.hw = w.hw; s.mw = w.mw; }
+      if (w.mm >= 0 && (s.mm < 0 || higher(w.hm, w.mm, s.hm, s.mm))) { s.hm = w.hm; s.mm = w.mm; }
+      s.plat = fmax(s.plat, w.plat); s.platw = fmax(s.platw, w.platw); nvmin = fmax(nvmin, w.nvmin);
+      s.s1 += w.s1; s.s2 += w.s2; s.a1 += w.a1; s.w1 += w.w1; s.w2 += w.w2;
     }
-    vmin = -nvmin;
+    s.vmin = -nvmin;
   }
   bool flag = false;                                           // the row needs its samples: stored-row path at the end of the call
   int why = 0;                                                 // (diagnostics: which rule flagged it)
-  if (imax < 0 || imax >= n) { imax = 0; flag = true; why |= 1; }
-  if (__syncthreads_or(abandoned ? 1 : 0)) { flag = true; why |= 1; }
-  // a tie that may outrank the best strict peak (plateaus are resolved from the stored row)
-  if (plat > -INFINITY && (mb < 0 || plat >= hb)) { flag = true; why |= 2; }
-  if (windowed && platw > -INFINITY && (mw < 0 || platw >= hw)) { flag = true; why |= 4; }
+  if (s.imax < 0 || s.imax >= n) { s.imax = 0; flag = true; why |= 1; }
+  if (__syncthreads_or(s.abandoned ? 1 : 0)) { flag = true; why |= 1; }
 
-  // ---- SNR (utils.py:238-250): totals minus the window around the maximum
-  const int wlo_s = imax - pa.snr_w > 0 ? imax - pa.snr_w : 0;
-  const int whi_s = imax + pa.snr_w < n ? imax + pa.snr_w : n;
-  const double nn = double(n - (whi_s - wlo_s));
-  const double o1 = s1 - w1, o2 = s2 - w2;
-  if (!(o2 >= 0.25 * s2)) { flag = true; why |= 8; }           // the window holds most of the energy: two-pass sum of the noise region
-  double var = (o2 - o1 * o1 / nn) / nn;
-  if (var < 0) var = 0;
-  const double noise = sqrt(var);
-  const double snr = noise == 0.0 ? INFINITY : vmax / noise;
-
-  // ---- primary threshold (utils.py:144-149): exact ('adaptive'), or an interval from the blocks' histogram windows
+  // ---- 'median' with a multiplier above 2: the threshold interval from the blocks' histogram windows
+  const bool interval = pa.method == 0 && !fa.cheb;
   double tlo = 0, thi = 0;
-  if (!want_median) {
-    double va = (s2 - a1 * a1 / double(n)) / double(n);
-    if (va < 0) va = 0;
-    tlo = thi = pa.mult * (a1 / double(n) + sqrt(va));         // utils.py:147
-  } else if (fa.cheb) {
-    // No histograms: at most half of the samples can have x^2 >= 2 mean(x^2) (Markov), so median(|corr|) <= sqrt(2 s2 / n).
-    // A peak at or above mult x that bound passes the threshold of utils.py:145 for certain - and the highest peak of a PHAT
-    // row stands 3 to 4 sigma above a median of 0.67 sigma, the bound is 1.41 sigma.  A candidate below the bound is not
-    // decided here: the row is flagged and the stored-row path computes its exact median.
-    thi = pa.mult * sqrt(2.0 * s2 / double(n)) * (1.0 + 1e-12);
-    tlo = -INFINITY;
-  } else {
+  if (interval) {
     const unsigned r1 = unsigned((n - 1) / 2), r2 = unsigned(n / 2);
     const BlockHist* bh = pa.bh + size_t(row) * S;
     bool have = S <= 144;
@@ -324,62 +403,7 @@ __device__ __forceinline__ void fin_row(const PeakArgs& pa, const FinArgs& fa, i
       why |= 16;
     }
   }
-
-  // ---- the fallback chain of utils.py:152-179 for ONE peak
-  const double mean_abs = a1 / double(n);
-  int branch = 0, sel = imax;
-  double sel_h = vmax;
-  bool argmax_fallback = false;
-  if (!flag) {
-    bool alt = false;
-    if (mb >= 0 && hb >= thi) {
-    } else if (mb >= 0 && hb >= tlo) {
-      flag = true;                                             // inside the median's interval
-      why |= 32;
-    } else {
-      branch |= PAL_BR_ALT_THRESHOLD;
-      alt = true;
-      if (!(mb >= 0 && hb >= mean_abs)) { branch |= PAL_BR_ARGMAX_NO_PEAKS; argmax_fallback = true; }
-    }
-    if (!flag && !argmax_fallback) {
-      if (!windowed) {
-        sel = mb; sel_h = hb;                                  // the highest peak of the row is kept by the distance rule
-      } else {
-        const double t_lo = alt ? mean_abs : tlo, t_hi = alt ? mean_abs : thi;
-        bool found = false;
-        if (mw >= 0 && hw >= t_hi) found = true;
-        else if (mw >= 0 && hw >= t_lo) { flag = true; why |= 64; }
-        if (!flag && !found) {                                 // no peak of the first search inside the window: mean(|corr|), then argmax
-          branch |= PAL_BR_WINDOW_RETRY;
-          if (mw >= 0 && hw >= mean_abs) found = true;
-          else { branch |= PAL_BR_ARGMAX_WINDOW; argmax_fallback = true; }
-        }
-        if (found) {
-          // the window's best peak is kept unless a HIGHER peak lies closer than `distance`; inside the window there is none,
-          // and a sample outside it is that close only to peaks within distance - 2 of the window's edge.  The margins' best
-          // peak stands for every peak there: only if IT is higher can the window's peak be suppressed (whether it is - the
-          // margin peak may be suppressed itself - is a chain the stored row resolves)
-          const bool near = mw - fa.win_lo < pa.dist - 1 || fa.win_hi - mw < pa.dist - 1;
-          if (near && mm >= 0 && higher(hm, mm, hw, mw)) { flag = true; why |= 128; }
-          else { sel = mw; sel_h = hw; }
-        }
-      }
-    }
-    if (argmax_fallback) { sel = imax; sel_h = vmax; }
-  }
-  if (tid == 0) {
-    fa.need[row] = flag ? 1 : 0;
-    if (flag) {
-      atomicAdd(fa.status + 4, 1);
-      for (int b = 0; b < 8; ++b)
-        if (why >> b & 1) atomicAdd(fa.status + 5 + b, 1);
-    } else {
-      pal_pair_record r;
-      r.k_sel = sel; r.branch = branch; r.k_argmax = imax; r.n_sel = 1;
-      r.cmax = vmax; r.cmin = vmin; r.snr = snr; r.sel_height = sel_h;
-      fa.table[row] = r;
-    }
-  }
+  fin_decide(pa, fa, row, s, flag, why, interval, tlo, thi, tid == 0);
 }
 
 }  // namespace pal
@@ -393,11 +417,6 @@ namespace pal {
 //   kColsFourStep  last pass of the four-step chirp convolution with register rows (conv_kernels.h k_colsreg_inv): a lane holds the
 //                  P1 = M1 points of one column of the 2^P2-column workspace, sample m = r 2^P2 + c, the last row is partial
 //                  (m < n); the wavefronts are NW neighbouring strips
-#if defined(PAL_ABL_FIN) && PAL_ABL_FIN == 9
-#define FIN_SYNC() ((void)0)                                    // timing experiment: no block barriers after the transform (invalid results)
-#else
-#define FIN_SYNC() __syncthreads()
-#endif
 enum { kColsDense = 0, kColsRader89 = 1, kColsStrips = 2, kColsFourStep = 3 };
 
 struct FinSrc {
@@ -546,27 +565,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
     if (!last) return;
     stamp();                                                   // 5
     if (wave != 0) return;                                     // ONE wavefront finishes the transform's rows (fin_row_wave)
-    bool late = false;
-    for (int q = lane; q < nblk * fa.pw; q += 64) {
-      int spins = 0;
-      while (ld_agent(fa.done + size_t(g) * nblk * fa.pw + q) != fa.epoch) {
-        if (++spins > kSpinLimit) { late = true; break; }
-        __builtin_amdgcn_s_sleep(8);
-      }
-    }
-    if (__ballot(late)) {                                      // the siblings' results are not there: both rows go through the stored-row path
-      if (lane < 2 && 2 * g + lane < rows) { fa.need[2 * g + lane] = 1; atomicAdd(fa.status + 4, 1); atomicAdd(fa.status + 13, 1); }
-      return;
-    }
-#pragma nounroll
-    for (int r = 0; r < 2; ++r)
-      if (2 * g + r < rows) fin_row_wave(pa, fa, 2 * g + r, N1, N2, lane);
-    stamp();                                                   // 6: both rows finished (last block only)
+    fin_rows_wave(pa, fa, g, nblk, rows, N1, N2, lane, stamp);
     return;
   }
-#if defined(PAL_ABL_FIN) && PAL_ABL_FIN == 1
-  { double acc = c0.x + c0.y; for (int i = 0; i < int(sizeof(ro) / sizeof(ro[0])); ++i) acc += ro[i].x * ro[i].y; if (acc == 1.2345e300) fa.status[3] = 1; return; }
-#endif
   // the samples of this lane, fn(value, t, exists): `value()` yields the sample (formed by two additions in the dense form, so
   // only where it is wanted); t and `exists` are wave-uniform.  Dense form: lag order (t = 0 for chunk 0 only, the chunk
   // ascending, the mirrors descending); Rader form: table order
@@ -593,7 +594,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
       }
     }
   };
-  FIN_SYNC();
+  __syncthreads();
 
   // ---- pass A: histogram of |x| (exact counts), maximum with its first index, minimum, sums
   const int nrow = 2 * g + 1 < rows ? 2 : 1;
@@ -627,21 +628,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
     }
     int im = own && vm > -INFINITY ? m2 + N2 * tm : -1;
     if (!own) { vm = -INFINITY; vn = INFINITY; s1 = s2 = a1 = 0; }
-#if defined(PAL_ABL_FIN) && PAL_ABL_FIN == 21
-    if (vm + vn + s1 + s2 + a1 == 1.2345e300 && im == 77) fa.status[3] = 1;
-    if (r == 1) return;
-    continue;
-#endif
     wave_arg63(vm, im, [](double v1, int i1, double v2, int i2) { return arg_better<0>(v1, i1, v2, i2); });
     vn = wave_min63(vn);
     s1 = wave_sum63(s1);
     s2 = wave_sum63(s2);
     a1 = wave_sum63(a1);
-#if defined(PAL_ABL_FIN) && PAL_ABL_FIN == 22
-    if (vm + vn + s1 + s2 + a1 == 1.2345e300 && im == 77) fa.status[3] = 1;
-    if (r == 1) return;
-    continue;
-#endif
     if (lane == 63) {
       wmax[wave][r] = im >= 0 ? vm : -INFINITY;
       FinPartial& w = res[wave][r];
@@ -652,7 +643,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
         st_agent16(fa.emax + ((size_t(2 * g + r) * pa.splits + cb) * 4 + wave) * 2, vm, double(fa.epoch) * kEpochUnit + double(im + 1));
     }
   }
-  FIN_SYNC();
+  __syncthreads();
   // ---- the block's median bin per row, then the window around it is published
   if (want_median) {
     constexpr int PER = kLogBins / LANES;
@@ -717,9 +708,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
     }
   }
   stamp();                                                     // 2: pass A, histogram windows, edge columns
-#if defined(PAL_ABL_FIN) && PAL_ABL_FIN == 2
-  return;
-#endif
 
   // ---- pass B: the highest strict peak behind the block's exact bound; a block whose bounded search found no peak
   //      searches all its samples (second round), so its result is exact
@@ -796,7 +784,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
         }
       }
     }
-    FIN_SYNC();
+    __syncthreads();
     if (round == 1) break;
     bool again = false;
 #pragma unroll
@@ -807,15 +795,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
       again = again || redo[r];
     }
     if (!again) break;                                         // (uniform: every lane read the same LDS words)
-    FIN_SYNC();
+    __syncthreads();
   }
   // ---- phase 2: the siblings' maxima (published long ago), then the SNR window sums of this block's samples
   stamp();                                                     // 3: pass B
-#if defined(PAL_ABL_FIN) && PAL_ABL_FIN == 3
-  return;
-#endif
   if (tid == 0) s_flag = 0;                                    // (1: a wavefront gave up waiting for the siblings' maxima)
-  FIN_SYNC();
+  __syncthreads();
   if (wave < 2 && 2 * g + wave < rows) {
     const int row = 2 * g + wave;
     double bv = 0;
@@ -841,7 +826,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
     wave_arg63(bv, bi, [](double v1, int i1, double v2, int i2) { return arg_better<0>(v1, i1, v2, i2); });
     if (lane == 63) s_imax[wave] = bi;
   }
-  FIN_SYNC();
+  __syncthreads();
   stamp();                                                     // 4: the row's argmax is known
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
@@ -866,7 +851,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
     w2 = wave_sum63(w2);
     if (lane == 63) { res[wave][r].w1 = w1; res[wave][r].w2 = w2; }
   }
-  FIN_SYNC();
+  __syncthreads();
   // ---- publish: lanes 0 / 1 merge the wavefronts of row p / q; then the block is done
   if (tid < 2 && 2 * g + tid < rows) {
     const int r = tid, row = 2 * g + r;
@@ -891,7 +876,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
     st_words(fa.parts + size_t(row) * pa.splits + cb, pt);
   }
   stores_done();                                               // this wavefront's stores (results, histogram windows, edge columns) have landed ...
-  FIN_SYNC();                                             // ... and so have the other wavefronts' before lane 0 announces the block
+  __syncthreads();                                             // ... and so have the other wavefronts' before lane 0 announces the block
   if (tid == 0) st_agent(fa.done + size_t(g) * nblk + cb, fa.epoch);
   stamp();                                                     // 5: published
   if (cb != nblk - 1) return;                                  // (uniform)
@@ -966,22 +951,7 @@ __global__ __launch_bounds__(256) void k_rows_lean(const double* __restrict__ co
   if (!last) return;
   stamp();                                                     // 5
   if (wave != 0) return;                                       // ONE wavefront finishes the transform's rows
-  bool late = false;
-  for (int q = lane; q < nblk * fa.pw; q += 64) {
-    int spins = 0;
-    while (ld_agent(fa.done + size_t(g) * nblk * fa.pw + q) != fa.epoch) {
-      if (++spins > kSpinLimit) { late = true; break; }
-      __builtin_amdgcn_s_sleep(8);
-    }
-  }
-  if (__ballot(late)) {
-    if (lane < 2 && 2 * g + lane < rows) { fa.need[2 * g + lane] = 1; atomicAdd(fa.status + 4, 1); atomicAdd(fa.status + 13, 1); }
-    return;
-  }
-#pragma nounroll
-  for (int r = 0; r < 2; ++r)
-    if (2 * g + r < rows) fin_row_wave(pa, fa, 2 * g + r, 0, W, lane);
-  stamp();                                                     // 6
+  fin_rows_wave(pa, fa, g, nblk, rows, 0, W, lane, stamp);
 }
 
 }  // namespace pal

@@ -193,7 +193,6 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
 
     // ---- pass B: the highest strict peak.  The maximum itself, if it is one (and single: equal samples are told apart by the
     //      search); else the samples at or above 0.8 V, else all of them - exact each time
-#if !defined(PAL_ABL_LEAN) || PAL_ABL_LEAN >= 2
     if (nhit == 1 && vpeak) {
       pt[r].hb = V; pt[r].mb = im; pt[r].plat = -INFINITY;
     } else {
@@ -221,13 +220,8 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
         if (mb >= 0 || pfloor == -INFINITY) break;            // (uniform)
       }
     }
-#endif
     // ---- the lag window and its margins: their highest strict peaks, whatever their height (a few slots meet them)
-#if defined(PAL_ABL_LEAN) && PAL_ABL_LEAN < 3
-    if (false) {
-#else
     if (wmask) {
-#endif
       double hq = -INFINITY, hg = -INFINITY, platw = -INFINITY;
       int mq = -1, mg = -1;
       for_slots(r, [&](double x, int slot) {
@@ -248,10 +242,6 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
     }
   }
   stamp();                                                     // 2: passes A and B
-#if defined(PAL_ABL_LEAN) && PAL_ABL_LEAN < 4
-  if (vn[0] + s1[0] + s2[0] + a1[0] + vn[1] + s1[1] + s2[1] + a1[1] + pt[0].hb + pt[1].hb + pt[0].hw + pt[1].hw == 1.2345e300) fa.status[3] = 1;
-  return false;
-#endif
 
   // ---- the grid's edge columns go to the finishing block as they are (blocks 0 and nblk - 1 only)
   if (edge_block) {                                            // (uniform)
@@ -337,10 +327,6 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
   }
   if (gave_up && lane == 0) atomicAdd(fa.status + 13, 1);
   stamp();                                                     // 3: the row's argmax, window sums
-#if defined(PAL_ABL_LEAN) && PAL_ABL_LEAN < 5
-  if (rmin + r1 + r2 + ra + pt[0].hb + pt[1].hb + pt[0].hw + pt[1].hw + w1[0] + w2[0] + w1[1] + w2[1] == 1.2345e300) fa.status[3] = 1;
-  return false;
-#endif
 
   // ---- the window sums' butterfly; lane r publishes row r's results, then the wavefront's `done` word follows
   {
@@ -357,9 +343,7 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
       st_words(fa.parts + (size_t(2 * g + lane) * S + cb) * PW + wave, o);
     }
   }
-#if !defined(PAL_ABL_LEAN) || PAL_ABL_LEAN != 6
   stores_done();                                               // this wavefront's stores (results, edge columns) have landed
-#endif
   if (lane == 0) st_agent(fa.done + (size_t(g) * nblk + cb) * PW + wave, fa.epoch);
   stamp();                                                     // 4: published
   return cb == nblk - 1;
@@ -367,36 +351,31 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
 
 
 // ---- the finishing WAVEFRONT: one row from the wavefronts' published results (64 lanes, uniform control flow; the counterpart of
-//      pfa_cols_fin.h fin_row for FinArgs.pw = 4 and no histograms - same rules, same order of the tests) ----
+//      pfa_cols_fin.h fin_row for FinArgs.pw = 4 and no histograms - the same fin_decide behind its own merge across the lanes) ----
 __device__ __forceinline__ void fin_row_wave(const PeakArgs& pa, const FinArgs& fa, int row, int N1, int N2, int lane) {
   const int S = pa.splits, n = pa.n, P = S * fa.pw;
   const bool windowed = fa.windowed != 0;
-  const bool want_median = pa.method == 0;
-  double vmax = 0, vmin = INFINITY, hb = 0, plat = -INFINITY, s1 = 0, s2 = 0, a1 = 0, w1 = 0, w2 = 0;
-  int imax = -1, mb = -1;
-  double hw = 0, hm = 0, platw = -INFINITY;
-  int mw = -1, mm = -1;
-  bool abandoned = false;
+  FinRow s;
   {
     const double* em = fa.emax + size_t(row) * P * 2;
     for (int q = lane; q < P; q += 64) {
       const double v = ld_agent(em + 2 * q);
       const int i = int(ld_agent(em + 2 * q + 1) - double(fa.epoch) * kEpochUnit) - 1;      // (complete: every wavefront of the transform is done)
-      if (i >= 0 && i < n && (imax < 0 || arg_better<0>(v, i, vmax, imax))) { vmax = v; imax = i; }
+      if (i >= 0 && i < n && (s.imax < 0 || arg_better<0>(v, i, s.vmax, s.imax))) { s.vmax = v; s.imax = i; }
     }
   }
   for (int q = lane; q < P; q += 64) {
     const FinPartial pt = ld_words(fa.parts + size_t(row) * P + q);
-    vmin = fmin(vmin, pt.vmin);
-    if (pt.mb >= 0 && (mb < 0 || higher(pt.hb, pt.mb, hb, mb))) { hb = pt.hb; mb = pt.mb; }
-    plat = fmax(plat, pt.plat);
-    s1 += pt.s1; s2 += pt.s2; a1 += pt.a1;
-    w1 += pt.w1; w2 += pt.w2;
-    abandoned = abandoned || pt.pad != 0;
+    s.vmin = fmin(s.vmin, pt.vmin);
+    if (pt.mb >= 0 && (s.mb < 0 || higher(pt.hb, pt.mb, s.hb, s.mb))) { s.hb = pt.hb; s.mb = pt.mb; }
+    s.plat = fmax(s.plat, pt.plat);
+    s.s1 += pt.s1; s.s2 += pt.s2; s.a1 += pt.a1;
+    s.w1 += pt.w1; s.w2 += pt.w2;
+    s.abandoned = s.abandoned || pt.pad != 0;
     if (windowed) {
-      if (pt.mw >= 0 && (mw < 0 || higher(pt.hw, pt.mw, hw, mw))) { hw = pt.hw; mw = pt.mw; }
-      if (pt.mm >= 0 && (mm < 0 || higher(pt.hm, pt.mm, hm, mm))) { hm = pt.hm; mm = pt.mm; }
-      platw = fmax(platw, pt.platw);
+      if (pt.mw >= 0 && (s.mw < 0 || higher(pt.hw, pt.mw, s.hw, s.mw))) { s.hw = pt.hw; s.mw = pt.mw; }
+      if (pt.mm >= 0 && (s.mm < 0 || higher(pt.hm, pt.mm, s.hm, s.mm))) { s.hm = pt.hm; s.mm = pt.mm; }
+      s.platw = fmax(s.platw, pt.platw);
     }
   }
   // the grid's first and last column: neighbours in another output index (m - 1 = (N2 - 1, t - 1), m + 1 = (0, t + 1))
@@ -413,32 +392,31 @@ __device__ __forceinline__ void fin_row_wave(const PeakArgs& pa, const FinArgs& 
     const bool pk = xl < x && xr < x;
     const bool inw = windowed && m >= fa.win_lo && m <= fa.win_hi;
     const bool inm = windowed && !inw && m >= fa.win_lo - (pa.dist - 1) && m <= fa.win_hi + (pa.dist - 1);
-    if (tie) plat = fmax(plat, x);
-    if (tie && (inw || inm)) platw = fmax(platw, x);
-    if (pk && (mb < 0 || higher(x, m, hb, mb))) { hb = x; mb = m; }
-    if (pk && inw && (mw < 0 || higher(x, m, hw, mw))) { hw = x; mw = m; }
-    if (pk && inm && (mm < 0 || higher(x, m, hm, mm))) { hm = x; mm = m; }
+    if (tie) s.plat = fmax(s.plat, x);
+    if (tie && (inw || inm)) s.platw = fmax(s.platw, x);
+    if (pk && (s.mb < 0 || higher(x, m, s.hb, s.mb))) { s.hb = x; s.mb = m; }
+    if (pk && inw && (s.mw < 0 || higher(x, m, s.hw, s.mw))) { s.hw = x; s.mw = m; }
+    if (pk && inm && (s.mm < 0 || higher(x, m, s.hm, s.mm))) { s.hm = x; s.mm = m; }
   }
   // across the lanes: everything ends uniform
-  uniform_arg_dense_lo(vmax, imax);
-  uniform_arg_dense_hi(hb, mb);
+  uniform_arg_dense_lo(s.vmax, s.imax);
+  uniform_arg_dense_hi(s.hb, s.mb);
   if (windowed) {
-    uniform_arg_dense_hi(hw, mw);
-    uniform_arg_sparse(hm, mm, [](double v1, int i1, double v2, int i2) { return higher(v1, i1, v2, i2); });
-    platw = uniform_max_sparse(platw);
+    uniform_arg_dense_hi(s.hw, s.mw);
+    uniform_arg_sparse(s.hm, s.mm, [](double v1, int i1, double v2, int i2) { return higher(v1, i1, v2, i2); });
+    s.platw = uniform_max_sparse(s.platw);
   }
-  plat = uniform_max_sparse(plat);
-  vmin = wave_bcast63(wave_min63r(vmin));
-  s1 = wave_bcast63(wave_sum63(s1)); s2 = wave_bcast63(wave_sum63(s2)); a1 = wave_bcast63(wave_sum63(a1));
-  w1 = wave_bcast63(wave_sum63(w1)); w2 = wave_bcast63(wave_sum63(w2));
-  abandoned = __ballot(abandoned) != 0;
+  s.plat = uniform_max_sparse(s.plat);
+  s.vmin = wave_bcast63(wave_min63r(s.vmin));
+  s.s1 = wave_bcast63(wave_sum63(s.s1)); s.s2 = wave_bcast63(wave_sum63(s.s2)); s.a1 = wave_bcast63(wave_sum63(s.a1));
+  s.w1 = wave_bcast63(wave_sum63(s.w1)); s.w2 = wave_bcast63(wave_sum63(s.w2));
 
   bool flag = false;                                           // the row needs its samples: stored-row path at the end of the call
   int why = 0;                                                 // (diagnostics: which rule flagged it)
-  if (imax < 0 || imax >= n) { imax = 0; flag = true; why |= 1; }
-  if (abandoned) { flag = true; why |= 1; }
+  if (s.imax < 0 || s.imax >= n) { s.imax = 0; flag = true; why |= 1; }
+  if (__ballot(s.abandoned) != 0) { flag = true; why |= 1; }
   if (fa.corr) {                                               // stored-row form: the SNR window from the row itself (written by this XCD's blocks)
-    const int lo = imax - pa.snr_w > 0 ? imax - pa.snr_w : 0, hi = imax + pa.snr_w < n ? imax + pa.snr_w : n;
+    const int lo = s.imax - pa.snr_w > 0 ? s.imax - pa.snr_w : 0, hi = s.imax + pa.snr_w < n ? s.imax + pa.snr_w : n;
     const double* rowp = fa.corr + size_t(row) * fa.stride;
     double u1 = 0, u2 = 0;
     for (int k = lo + lane; k < hi; k += 64) {
@@ -446,87 +424,33 @@ __device__ __forceinline__ void fin_row_wave(const PeakArgs& pa, const FinArgs& 
       u1 += x;
       u2 = __builtin_fma(x, x, u2);
     }
-    w1 = wave_bcast63(wave_sum63(u1));
-    w2 = wave_bcast63(wave_sum63(u2));
+    s.w1 = wave_bcast63(wave_sum63(u1));
+    s.w2 = wave_bcast63(wave_sum63(u2));
   }
-  // a tie that may outrank the best strict peak (plateaus are resolved from the stored row)
-  if (plat > -INFINITY && (mb < 0 || plat >= hb)) { flag = true; why |= 2; }
-  if (windowed && platw > -INFINITY && (mw < 0 || platw >= hw)) { flag = true; why |= 4; }
+  fin_decide(pa, fa, row, s, flag, why, false, 0, 0, lane == 0);
+}
 
-  // ---- SNR (utils.py:238-250): totals minus the window around the maximum
-  const int wlo_s = imax - pa.snr_w > 0 ? imax - pa.snr_w : 0;
-  const int whi_s = imax + pa.snr_w < n ? imax + pa.snr_w : n;
-  const double nn = double(n - (whi_s - wlo_s));
-  const double o1 = s1 - w1, o2 = s2 - w2;
-  if (!(o2 >= 0.25 * s2)) { flag = true; why |= 8; }           // the window holds most of the energy: two-pass sum of the noise region
-  double var = (o2 - o1 * o1 / nn) / nn;
-  if (var < 0) var = 0;
-  const double noise = sqrt(var);
-  const double snr = noise == 0.0 ? INFINITY : vmax / noise;
-
-  // ---- primary threshold (utils.py:144-149): exact ('adaptive'), or the bound on the median (see pfa_cols_fin.h fin_row)
-  double tlo = 0, thi = 0;
-  if (!want_median) {
-    double va = (s2 - a1 * a1 / double(n)) / double(n);
-    if (va < 0) va = 0;
-    tlo = thi = pa.mult * (a1 / double(n) + sqrt(va));         // utils.py:147
-  } else {
-    thi = pa.mult * sqrt(2.0 * s2 / double(n)) * (1.0 + 1e-12);
-    tlo = -INFINITY;
-  }
-
-  // ---- the fallback chain of utils.py:152-179 for ONE peak
-  const double mean_abs = a1 / double(n);
-  int branch = 0, sel = imax;
-  double sel_h = vmax;
-  bool argmax_fallback = false;
-  if (!flag) {
-    bool alt = false;
-    if (mb >= 0 && hb >= thi) {
-    } else if (mb >= 0 && hb >= tlo) {
-      flag = true;                                             // inside the median's interval
-      why |= 32;
-    } else {
-      branch |= PAL_BR_ALT_THRESHOLD;
-      alt = true;
-      if (!(mb >= 0 && hb >= mean_abs)) { branch |= PAL_BR_ARGMAX_NO_PEAKS; argmax_fallback = true; }
-    }
-    if (!flag && !argmax_fallback) {
-      if (!windowed) {
-        sel = mb; sel_h = hb;                                  // the highest peak of the row is kept by the distance rule
-      } else {
-        const double t_lo = alt ? mean_abs : tlo, t_hi = alt ? mean_abs : thi;
-        bool found = false;
-        if (mw >= 0 && hw >= t_hi) found = true;
-        else if (mw >= 0 && hw >= t_lo) { flag = true; why |= 64; }
-        if (!flag && !found) {                                 // no peak of the first search inside the window: mean(|corr|), then argmax
-          branch |= PAL_BR_WINDOW_RETRY;
-          if (mw >= 0 && hw >= mean_abs) found = true;
-          else { branch |= PAL_BR_ARGMAX_WINDOW; argmax_fallback = true; }
-        }
-        if (found) {
-          // (pfa_cols_fin.h fin_row: only a HIGHER peak in the margins can suppress the window's best peak)
-          const bool near = mw - fa.win_lo < pa.dist - 1 || fa.win_hi - mw < pa.dist - 1;
-          if (near && mm >= 0 && higher(hm, mm, hw, mw)) { flag = true; why |= 128; }
-          else { sel = mw; sel_h = hw; }
-        }
-      }
-    }
-    if (argmax_fallback) { sel = imax; sel_h = vmax; }
-  }
-  if (lane == 0) {
-    fa.need[row] = flag ? 1 : 0;
-    if (flag) {
-      atomicAdd(fa.status + 4, 1);
-      for (int b = 0; b < 8; ++b)
-        if (why >> b & 1) atomicAdd(fa.status + 5 + b, 1);
-    } else {
-      pal_pair_record r;
-      r.k_sel = sel; r.branch = branch; r.k_argmax = imax; r.n_sel = 1;
-      r.cmax = vmax; r.cmin = vmin; r.snr = snr; r.sel_height = sel_h;
-      fa.table[row] = r;
+// ---- the tail of a per-wavefront pass, in wavefront 0 of the transform's last block: wait for every wavefront's `done` word, then
+//      finish rows 2 g and 2 g + 1 and take the kernel's stamp 6.  When the siblings' results are not there in time both rows go through
+//      the stored-row path instead
+template <class STAMP>
+__device__ __forceinline__ void fin_rows_wave(const PeakArgs& pa, const FinArgs& fa, int g, int nblk, int rows, int N1, int N2, int lane, STAMP&& stamp) {
+  bool late = false;
+  for (int q = lane; q < nblk * fa.pw; q += 64) {
+    int spins = 0;
+    while (ld_agent(fa.done + size_t(g) * nblk * fa.pw + q) != fa.epoch) {
+      if (++spins > kSpinLimit) { late = true; break; }
+      __builtin_amdgcn_s_sleep(8);
     }
   }
+  if (__ballot(late)) {
+    if (lane < 2 && 2 * g + lane < rows) { fa.need[2 * g + lane] = 1; atomicAdd(fa.status + 4, 1); atomicAdd(fa.status + 13, 1); }
+    return;
+  }
+#pragma nounroll
+  for (int r = 0; r < 2; ++r)
+    if (2 * g + r < rows) fin_row_wave(pa, fa, 2 * g + r, N1, N2, lane);
+  stamp();                                                     // 6: both rows finished (last block only)
 }
 
 }  // namespace pal

@@ -76,7 +76,7 @@ int pal_create(int device, pal_handle* out);
 void pal_destroy(pal_handle h);
 const char* pal_last_error(pal_handle h); /* h may be NULL: error of the last failed pal_create */
 int pal_synchronize(pal_handle h);
-/* transforms processed per launch group (workspace = chunk * M * 16 B); 0 keeps the default: 128, and for the pair
+/* transforms processed per launch group (workspace = chunk * M * 16 B); 0 restores the default: 128, and for the pair
  * pipeline (two pairs per transform) 240 where one workspace slot stays below 1 GiB, 32 at least */
 int pal_set_chunk(pal_handle h, int chunk);
 /* Plans (chirps, chirp spectra, prime-factor tables: a few MB per transform length) are built on first use and cached

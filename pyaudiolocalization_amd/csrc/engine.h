@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/pal_hip.h"
+#include "fin_scratch.h"
 #include "fft_core.h"
 
 namespace pal {
@@ -112,7 +113,8 @@ struct Engine {
   bool allow_big = true;           // PAL_PFA_BIG=0: no register-resident row tiles (N2 <= 2048 only, as in round 1)
   int pfa_sub = 0;                 // transforms per row/column pass of the prime-factor route (PAL_PFA_SUB; 0 = whole group)
   std::string err;
-  int chunk = 128;                              // transforms per launch group (forward spectra, simulation, synchronisation)
+  static constexpr int kDefaultChunk = 128;
+  int chunk = kDefaultChunk;                    // transforms per launch group (forward spectra, simulation, synchronisation)
   bool chunk_auto = true;                       // pair pipeline: 240 transforms per group where a workspace slot stays <= 1 GiB
                                                 // (480 rows: the finish launch's workgroups, two per CU, leave slots free
                                                 //  beside the other streams' launches - 256 measured 3 % less than 240)
@@ -216,7 +218,9 @@ struct Engine {
   bool fin_cols = true;       // PAL_FIN=0: the fused column pass always stores the correlation rows for a finish launch (pfa_cols_stats.h) instead
                               // of finishing the rows itself without storing them (pfa_cols_fin.h: one peak per row, nobody asks for `corr`)
   unsigned fin_epoch[3] = {};   // launches of the finishing column pass per stream slot (pfa_cols_fin.h: validity tag of what its blocks exchange)
-  size_t fin_bytes[3] = {};
+  FinKey fin_key[3];            // the layout of the slot's latest launch (fin_scratch.h: another one zeroes the block)
+  unsigned fin_wrap = kFinEpochWrap;   // PAL_DEBUG_FIN_WRAP=<n>: the epoch bound (tests of the reset at the wrap)
+  int fin_giveup = 0;           // PAL_DEBUG_FIN_GIVEUP=1: every bounded wait of the pass gives up at once (tests of the stored-row repair)
   bool allow_r89 = true;      // PAL_R89=0: dense 89-point column DFTs instead of Rader's 8 x 11 convolution (pfa_rader89.h)
   bool fuse_peaks = true;     // PAL_FUSED=0: separate column pass + pivot / stream launches instead of the fused column pass +
                               // peak statistics (pfa_cols_stats.h) where that applies

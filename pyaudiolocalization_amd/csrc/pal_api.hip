@@ -341,6 +341,10 @@ int pal_create(int device, pal_handle* out) {
   if (env) e->lean_store = atoi(env) != 0;
   env = getenv("PAL_DEBUG_MEMO");
   if (env) e->debug_memo = atoi(env);
+  env = getenv("PAL_DEBUG_FIN_WRAP");
+  if (env && atoi(env) >= 2) e->fin_wrap = unsigned(atoi(env));
+  env = getenv("PAL_DEBUG_FIN_GIVEUP");
+  if (env) e->fin_giveup = atoi(env) != 0 ? 1 : 0;
   env = getenv("PAL_PFA_SUB");
   if (env) e->pfa_sub = atoi(env);
   env = getenv("PAL_MAX_PLANS");
@@ -411,6 +415,7 @@ int pal_set_chunk(pal_handle h, int chunk) {
   ENGINE(h);
   if (chunk < 0 || chunk > 4096) return e->fail(PAL_ERR_INVALID, "chunk %d outside 0..4096", chunk);
   if (chunk > 0) { e->chunk = chunk; e->chunk_auto = false; }
+  else { e->chunk = Engine::kDefaultChunk; e->chunk_auto = true; }   // 0: the default and the automatic pair group size again
   return PAL_OK;
 }
 

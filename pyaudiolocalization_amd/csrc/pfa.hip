@@ -423,15 +423,11 @@ int Engine::fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, int gri
                       int* need, int slot, hipStream_t on, PeakArgs& a, FinArgs& fa, unsigned& nwg, int G) {
   const int n = pl.n;
   PAL_TRY(peaks_setup(nullptr, 0, rows, n, n2, prm, nblk, grid_cols, on, a));
-  // per-stream scratch of the finishing pass: [done words G x blocks | emax | parts | edge]
-  const int Gmax = pair_group(n);
+  // per-stream scratch of the finishing pass: [done words G x blocks | emax | parts | edge] (fin_scratch.h)
   // (`done` words and FinPartial entries: room for one per WAVEFRONT of a block, pfa_fin_lean.h)
-  const size_t off_emax = (size_t(Gmax) * nblk * 6 * sizeof(unsigned) + 127) & ~size_t(127);
-  const size_t off_parts = (off_emax + size_t(2 * Gmax) * nblk * 12 * sizeof(double) + 127) & ~size_t(127);
-  const size_t off_edge = (off_parts + size_t(2 * Gmax) * nblk * 6 * sizeof(FinPartial) + 127) & ~size_t(127);
-  const size_t total = off_edge + size_t(2 * Gmax) * 4 * grid_rows * sizeof(double);
+  const FinLayout lay = fin_layout(pair_group(n), nblk, grid_rows);
   void* sp = nullptr;
-  PAL_TRY(scratch(16 + slot, total, &sp));
+  PAL_TRY(scratch(16 + slot, lay.total, &sp));
   char* base = static_cast<char*>(sp);
   int* status = nullptr;
   {
@@ -442,16 +438,23 @@ int Engine::fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, int gri
   fa.table = table;
   fa.need = need;
   fa.done = reinterpret_cast<unsigned*>(base);
-  // launch number of this stream's scratch: entries of earlier launches fail the comparison (no resets, no counters)
-  if (ws_bytes[16 + slot] != fin_bytes[slot] || fin_epoch[slot] >= (1u << 20)) {     // new (zeroed) scratch, or the number would outgrow a double's integers
-    PAL_HIP(hipMemsetAsync(sp, 0, total, on));
-    fin_bytes[slot] = ws_bytes[16 + slot];
+  // launch number of this stream's scratch: entries of earlier launches of the same layout fail the comparison.  Another layout
+  // (or a block that grew), or a number that would outgrow a double's integers, zeroes the whole block and starts again at 1
+  FinKey key;
+  key.gmax = pair_group(n);
+  key.nblk = nblk;
+  key.grid_rows = grid_rows;
+  key.block = ws_bytes[16 + slot];
+  if (fin_must_zero(fin_key[slot], key, fin_epoch[slot], fin_wrap)) {
+    PAL_HIP(hipMemsetAsync(sp, 0, ws_bytes[16 + slot], on));
+    fin_key[slot] = key;
     fin_epoch[slot] = 0;
   }
   fa.epoch = ++fin_epoch[slot];
-  fa.emax = reinterpret_cast<double*>(base + off_emax);
-  fa.parts = reinterpret_cast<FinPartial*>(base + off_parts);
-  fa.edge = reinterpret_cast<double*>(base + off_edge);
+  fa.emax = reinterpret_cast<double*>(base + lay.off_emax);
+  fa.parts = reinterpret_cast<FinPartial*>(base + lay.off_parts);
+  fa.edge = reinterpret_cast<double*>(base + lay.off_edge);
+  fa.giveup = fin_giveup;
   fa.status = status;
   // the lag window |m - (n2 - 1)| / fs <= max_expected_delay (utils.py:163) as sample indices, with the reference's arithmetic
   fa.pw = 1;

@@ -39,6 +39,7 @@
 #pragma once
 #include <climits>
 
+#include "fin_scratch.h"
 #include "pfa_cols_stats.h"
 #include "reduce.h"
 #include "wave_reduce.h"
@@ -53,7 +54,7 @@ struct FinPartial {               // what one column block hands to the finishin
   double w1, w2;                  // sum x, sum x^2 of the block's samples inside the SNR window around the row's maximum
   int mb, mw, mm, pad;
 };
-static_assert(sizeof(FinPartial) == 104, "thirteen words");
+static_assert(sizeof(FinPartial) == 104 && sizeof(FinPartial) == kFinPartialBytes, "thirteen words (fin_scratch.h)");
 
 struct FinArgs {
   pal_pair_record* table;         // [rows] records of this launch group
@@ -62,6 +63,7 @@ struct FinArgs {
   double* edge;                   // [rows][4][N1] columns 0, 1, N2 - 2, N2 - 1 of the grid
   double* emax;                   // [rows][S][4][2] every wavefront's (maximum, 2^32 epoch + 1 + first index of it), ONE 16-byte store behind pass A
   unsigned epoch;                 // number of this launch on its stream (> 0; the scratch starts zeroed): stale entries fail the comparison, nothing is reset
+  int giveup;                     // 1 (PAL_DEBUG_FIN_GIVEUP): every bounded wait gives up without polling - the rows take the stored-row path
   FinPartial* parts;              // [rows][S]
   int* status;                    // engine status words (bit 2 of word 0: a wait timed out; word 4: flagged rows)
   int win_lo, win_hi;             // lag window as sample indices, |m - (n2 - 1)| / fs <= max_expected_delay (win_lo > win_hi: empty)
@@ -807,8 +809,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
     int bi = -1;
     const double* em = fa.emax + size_t(row) * pa.splits * 8;
     const double want = double(fa.epoch);
-    bool late = false;
-    for (int q = lane; q < pa.splits * 4; q += 64) {           // (entry = block * 4 + wavefront; idle wavefronts never write theirs)
+    bool late = fa.giveup != 0;
+    for (int q = lane; !fa.giveup && q < pa.splits * 4; q += 64) {   // (entry = block * 4 + wavefront; idle wavefronts never write theirs)
       if ((q & 3) >= nact) continue;
       double v = 0, code = 0;
       int spins = 0;
@@ -883,8 +885,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
 
   // ---- the last block of the transform waits for its siblings' results and finishes both rows
   {
-    bool late = false;
-    for (int q = tid; q < nblk - 1; q += LANES) {
+    bool late = fa.giveup != 0;
+    for (int q = tid; !fa.giveup && q < nblk - 1; q += LANES) {
       int spins = 0;
       while (ld_agent(fa.done + size_t(g) * nblk + q) != fa.epoch) {
         if (++spins > kSpinLimit) { late = true; break; }

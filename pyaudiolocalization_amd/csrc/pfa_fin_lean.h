@@ -291,8 +291,8 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
     int bi = -1;
     const double* em = fa.emax + size_t(row) * S * PW * 2;
     const double want = double(fa.epoch);
-    bool late = false;
-    for (int q = lane; q < S * PW; q += 64) {
+    bool late = fa.giveup != 0;
+    for (int q = lane; !fa.giveup && q < S * PW; q += 64) {
       double v = 0, code = 0;
       int spins = 0;
       for (;;) {                                               // (the entry of this launch: its second word carries the launch number)
@@ -435,8 +435,8 @@ __device__ __forceinline__ void fin_row_wave(const PeakArgs& pa, const FinArgs& 
 //      the stored-row path instead
 template <class STAMP>
 __device__ __forceinline__ void fin_rows_wave(const PeakArgs& pa, const FinArgs& fa, int g, int nblk, int rows, int N1, int N2, int lane, STAMP&& stamp) {
-  bool late = false;
-  for (int q = lane; q < nblk * fa.pw; q += 64) {
+  bool late = fa.giveup != 0;                                  // (PAL_DEBUG_FIN_GIVEUP=1: no polls, both rows flagged)
+  for (int q = lane; !fa.giveup && q < nblk * fa.pw; q += 64) {
     int spins = 0;
     while (ld_agent(fa.done + size_t(g) * nblk * fa.pw + q) != fa.epoch) {
       if (++spins > kSpinLimit) { late = true; break; }

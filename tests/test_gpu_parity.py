@@ -629,6 +629,9 @@ def test_pair_group_size_rule(engine):
         assert fresh.pair_group_size(1 << 20) == 32
         fresh.set_chunk(7)
         assert fresh.pair_group_size(44100) == 7
+        fresh.set_chunk(0)                                      # 0: the automatic size again (include/pal_hip.h)
+        assert fresh.pair_group_size(44100) == 240
+        assert fresh.pair_group_size(1 << 20) == 32
     finally:
         fresh.close()
 
@@ -639,8 +642,15 @@ def test_chunk_size_does_not_change_results(engine):
     a = engine.gcc_phat_all_pairs(frames, 16000.0, max_expected_delay=0.003)
     engine.set_chunk(3)
     b = engine.gcc_phat_all_pairs(frames, 16000.0, max_expected_delay=0.003)
-    engine.set_chunk(32)
+    engine.set_chunk(0)                                         # the session engine goes back to the sizes production runs
     assert a.tobytes() == b.tobytes()
+    from pyaudiolocalization_amd import Engine
+    fresh = Engine(engine.device)
+    try:
+        for length in (1500, 44100, 200000):
+            assert engine.pair_group_size(length) == fresh.pair_group_size(length), length
+    finally:
+        fresh.close()
 
 
 def test_metric_frames_full_table(engine, golden):

@@ -158,17 +158,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
   }
   __syncthreads();
   // ---- the cyclic convolution: first stage along axis R1 (in place), then the shared stages
-  using AX = Axes<R1, R2, R3>;
-  {
-    const int t1 = tid / (L / R1), i1 = tid % (L / R1);
-    cd v[R1];
-    if (tid < 2 * (L / R1)) {
-      axis_load<R1>(tile, t1, AX::base1(i1), AX::kStride1, v);
-      dft_sym<R1, false>(v);
-      axis_store<R1>(tile, t1, AX::base1(i1), AX::kStride1, v);
-    }
-    __syncthreads();
-  }
+  axis1_stage<R1, R2, R3, false>(tile, tid);
+  __syncthreads();
   rader_convolve<R1, R2, R3>(tile, a.bhat, total, tid);
   // ---- epilogue: output position p = pos(q) holds bin k2 = g^-q: Z[k1, k2] = x[0] + C0[pos(-q)] and
   //      Z[N1 - k1, N2 - k2] = x'[0] + C1[pos(-q + L/2)] (-1 = g^(L/2)).  pos() is a ring isomorphism, so both are

@@ -39,6 +39,20 @@ struct PfaRaderArgs {
   int xcd;               // 1: XCD-aware order of the workgroups (row_work_item, pfa_kernels.h)
 };
 
+// One stage along axis R1 of both tiles: 2 L / R1 = 180 butterflies on the first three wavefronts (the fourth has none)
+template <int R1, int R2, int R3, bool INV>
+__device__ __forceinline__ void axis1_stage(const PlainTile& tile, int tid) {
+  using AX = Axes<R1, R2, R3>;
+  constexpr int NB = AX::L / R1;
+  if (tid < 2 * NB) {
+    const int t = tid / NB, i = tid % NB;
+    cd v[R1];
+    axis_load<R1>(tile, t, AX::base1(i), AX::kStride1, v);
+    dft_sym<R1, INV>(v);
+    axis_store<R1>(tile, t, AX::base1(i), AX::kStride1, v);
+  }
+}
+
 // Stages 2-5 of the cyclic convolution on two L-point tiles in LDS (the first stage, along axis R1, has filled them):
 // in prime-factor coordinates (mixed_radix.h) the convolution is three-dimensional and its stages are plain DFTs along
 // one axis each, in place and without twiddles: forward along R2, the seam along R3 (forward DFT, x the kernel's 3-D
@@ -82,21 +96,12 @@ __device__ __forceinline__ void rader_convolve(const PlainTile& tile, const cd* 
     }
     __syncthreads();
   }
-  {
-    // (the radix-R1 stages have 2 L / R1 = 180 butterflies: packed onto the first three wavefronts, the fourth only waits)
-    const int t1 = tid / (L / R1), i1 = tid % (L / R1);
-    cd v[R1];
-    if (tid < 2 * (L / R1)) {
-      axis_load<R1>(tile, t1, AX::base1(i1), AX::kStride1, v);
-      dft_sym<R1, true>(v);
-      axis_store<R1>(tile, t1, AX::base1(i1), AX::kStride1, v);
-    }
-    __syncthreads();
-  }
+  axis1_stage<R1, R2, R3, true>(tile, tid);
+  __syncthreads();
 }
 
 template <int R1, int R2, int R3>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_pfa_rows_rader(PfaRaderArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_pfa_rows_rader(PfaRaderArgs a) {
   constexpr int L = R1 * R2 * R3, HALF = 128;
   static_assert(L / R1 <= HALF && L / R2 <= HALF && L / R3 <= HALF, "one butterfly per lane and stage");
   __shared__ cd data[2 * L];
@@ -125,12 +130,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
   const cd* sc = second ? a.SP + size_t(q.z) * mic + off : sa;
   const cd* sd = second ? a.SP + size_t(q.w) * mic + off : sb;
   const double keep2 = second ? 1.0 : 0.0;
-  int ri[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int e = tid + 256 * u;
-    ri[u] = a.ridx[e < N2 ? e : N2 - 1];
-  }
   // tile 0: R^p + i R^q at (k1, e);  tile 1: conj(R^p) + i conj(R^q) = the reversed row N1 - k1, held at the SAME
   // positions (it is transformed as the reversed sequence and its outputs are stored reversed)
   constexpr int NB1 = L / R1, HR = (R1 + 1) / 2;              // 90 butterflies per tile, 6 inputs per half-wavefront
@@ -169,6 +168,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
   rader_convolve<R1, R2, R3>(tile, a.bhat, total, tid);
   stamp();
   // ---- epilogue: X[e] = x[0] + C[log_g e] (X[0] = sum of the inputs), column twiddle, store
+  int ri[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int e = tid + 256 * u;
+    ri[u] = a.ridx[e < N2 ? e : N2 - 1];
+  }
   const cd x0 = cscale(dc[0], a.scale), z0 = cscale(dc[1], a.scale);
   const cd sum0 = cscale(total[0] + dc[0], a.scale), sum1 = cscale(total[1] + dc[1], a.scale);
   const int kr = k1 ? N1 - k1 : 0;

@@ -530,12 +530,10 @@ int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4
   const int chunk = pair_group(n);   // (shadows the engine-wide group size: larger groups amortise launch tails and the peak kernels' fixed costs)
   const cd* permuted = spectra;   // forward_spectra wrote the (k mod N1, k mod N2) layout when the plan has the split
   (void)nspec;
-  // Launch groups alternate between two HIP streams, each with its own workspace and correlation buffer: the
-  // memory-bound head and tail of one group's kernels overlap the LDS/VALU-bound middle of the other's, and the
-  // peak kernel of group g runs beside the FFT passes of group g+1.  Same-slot reuse is ordered by the stream.
-  const bool two = (overlap == 1 || overlap == 3) && table != nullptr;
-  const int nslot = two ? (overlap == 3 ? 3 : 2) : 1;
-  const bool split = overlap == 2 && table != nullptr;        // transforms on `stream`, peak selection on `stream2`
+  // Launch groups rotate over three HIP streams, each with its own workspace and correlation buffer: the
+  // memory-bound head and tail of one group's kernels overlap the LDS/VALU-bound middle of the others', and the
+  // peak kernels of group g run beside the FFT passes of group g+1.  Same-slot reuse is ordered by the stream.
+  const int nslot = !one_stream && table != nullptr ? 3 : 1;
   const size_t wpoints = size_t(chunk) * (pfa ? size_t(n) : c.M());
   void* wsp = nullptr;
   PAL_TRY(scratch(0, size_t(nslot) * wpoints * sizeof(cd), &wsp));
@@ -543,7 +541,7 @@ int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4
   const size_t stride = corr_out ? size_t(n) : (size_t(n) + 1) & ~size_t(1);
   const size_t buf_doubles = size_t(2 * chunk) * stride;
   void* p = nullptr;
-  PAL_TRY(scratch(1, size_t(nslot > 2 ? nslot : 2) * buf_doubles * sizeof(double), &p));
+  PAL_TRY(scratch(1, size_t(nslot) * buf_doubles * sizeof(double), &p));
   double* cbuf = static_cast<double*>(p);
   const int64_t ntr = (npairs + 1) / 2;
   int* zero_rows = nullptr;
@@ -555,44 +553,42 @@ int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4
     PAL_HIP(hipGetLastError());
   }
   // the finishing column pass (pfa_cols_fin.h) writes one flag per pair: 1 = resolved at the end of this call from stored rows
-  const bool fin = table && !split && !corr_out && !ksel_multi &&
-                   (pfa ? pfa_sub == 0 && pfa_can_finish(pl, prm) : fourstep_can_finish(pl, prm));
+  const bool fin = table && pfa && !corr_out && !ksel_multi && pfa_can_finish(pl, prm);
   // stored rows + per-wavefront statistics (pfa_fin_lean.h with FinArgs.corr): the caller wants corr, or the plan has no finishing form
-  const bool lean = !fin && pfa && table && !split && !ksel_multi && pfa_sub == 0 && pfa_can_lean_store(pl, prm);
+  const bool lean = !fin && pfa && table && !ksel_multi && pfa_can_lean_store(pl, prm);
   // rows of any other route: their statistics in one launch over the stored rows (k_rows_lean)
   // (calls of at least 200 000 pairs: the end-of-call count and the flagged rows' second pass - 1.8 % of the rows at C5's lag window -
   //  cost the 30 000 - 80 000-pair calls of the stream chain more than the launch saves, and stall its host: 480 - 497 against 527 - 535 frames/s)
-  const bool rlean = !fin && !lean && table && !split && !ksel_multi && npairs >= rows_lean_min && rows_can_lean(pl, prm) &&
-                     !(pfa && pfa_sub == 0 && pfa_can_fuse(pl));
+  const bool rlean = !fin && !lean && table && !ksel_multi && npairs >= rows_lean_min && rows_can_lean(pl, prm) &&
+                     !(pfa && pfa_can_fuse(pl));
   int* need = nullptr;
   if (fin || lean || rlean) {
     void* np = nullptr;
     PAL_TRY(scratch(19, (size_t(2 * npairs) + 64) * sizeof(int), &np));     // [flags | list | count]
     need = static_cast<int*>(np);
   }
-  if (two || split) {   // the other streams start after everything already queued on `stream` (spectra, pair table)
-    PAL_HIP(hipEventRecord(ev_corr[0], stream));
-    PAL_HIP(hipStreamWaitEvent(stream2, ev_corr[0], 0));
-    if (nslot == 3) PAL_HIP(hipStreamWaitEvent(stream3, ev_corr[0], 0));
+  if (nslot == 3) {   // the other streams start after everything already queued on `stream` (spectra, pair table)
+    PAL_HIP(hipEventRecord(ev_fork, stream));
+    PAL_HIP(hipStreamWaitEvent(stream2, ev_fork, 0));
+    PAL_HIP(hipStreamWaitEvent(stream3, ev_fork, 0));
   }
   // one launch group; a failure leaves through the common exit below (side streams joined, sampling gate restored)
   auto run_group = [&](int64_t t0, int64_t group) -> int {
     const int G = int(ntr - t0 < chunk ? ntr - t0 : chunk);
     const int64_t p0 = 2 * t0;
     const int rows = int(npairs - p0 < 2 * G ? npairs - p0 : 2 * G);
-    const int slot = two ? int(group % nslot) : (split ? int(group & 1) : 0);
-    hipStream_t on = two ? (slot == 0 ? stream : (slot == 1 ? stream2 : stream3)) : stream;
+    const int slot = int(group % nslot);
+    hipStream_t on = slot == 0 ? stream : (slot == 1 ? stream2 : stream3);
     prof_gate = prof_every <= 1 || (prof_tick++ % prof_every) == 0;
-    cd* Wg = W + (two ? size_t(slot) * wpoints : 0);
+    cd* Wg = W + size_t(slot) * wpoints;
     // odd tail with a caller buffer: the imaginary half of the last transform has no destination row there
     const bool via_scratch = !corr_out || rows < 2 * G;
     double* crow = via_scratch ? cbuf + size_t(slot) * buf_doubles : corr_out + size_t(p0) * stride;
-    if (split && group >= 2) PAL_HIP(hipStreamWaitEvent(stream, ev_peaks[slot], 0));   // group - 2 is done with this buffer
-    const bool fused = pfa && table && !split && pfa_sub == 0 && pfa_can_fuse(pl);
+    const bool fused = pfa && table && pfa_can_fuse(pl);
     if (lean) {
       PAL_TRY(pfa_pair_group_fin(pl, permuted, quads + t0, G, rows, Wg, zero_rows ? zero_rows + p0 : nullptr, prm, n2, table + p0, need + p0,
                                  slot, on, crow, stride));
-    } else if (fin && pfa) {
+    } else if (fin) {
       // nobody reads the correlation rows: the column pass finishes them without storing them (pfa_cols_fin.h)
       PAL_TRY(pfa_pair_group_fin(pl, permuted, quads + t0, G, rows, Wg, zero_rows ? zero_rows + p0 : nullptr, prm, n2, table + p0, need + p0,
                                  slot, on));
@@ -600,40 +596,21 @@ int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4
       PAL_TRY(pfa_pair_group_fused(pl, permuted, quads + t0, G, rows, Wg, crow, stride, zero_rows ? zero_rows + p0 : nullptr, prm, n2, table + p0,
                                    ksel_multi ? ksel_multi + p0 * PAL_MAX_PEAKS : nullptr, on));
     } else if (pfa) {
-      // sub-groups: the Y of a sub-group (1.4 MB per transform) is still in the Infinity Cache when the column
-      // pass reads it back, while the peak kernels keep whole launch groups (their fixed costs want many rows)
-      const int sub = pfa_sub > 0 && pfa_sub < G ? pfa_sub : G;
-      for (int g0 = 0; g0 < G; g0 += sub) {
-        const int Gs = G - g0 < sub ? G - g0 : sub;
-        PAL_TRY(pfa_pair_group(pl, permuted, quads + t0 + g0, Gs, Wg, crow + size_t(2 * g0) * stride, stride,
-                               zero_rows ? zero_rows + p0 + 2 * g0 : nullptr, on));
-      }
+      PAL_TRY(pfa_pair_group(pl, permuted, quads + t0, G, Wg, crow, stride, zero_rows ? zero_rows + p0 : nullptr, on));
     } else {
       PairLoader ld{spectra, quads + t0, n, pl.H, pl.w};
       PAL_TRY(launch_cols_fwd(e, c, G, ld, Wg, on));
       PAL_TRY(launch_rows(e, c, G, Wg, true, 1.0, on));
-      if (fin) {
-        // the last pass finishes its rows itself: no correlation rows in HBM, no statistics launches (pfa_cols_fin.h)
-        PAL_TRY(fourstep_pair_group_fin(pl, Wg, G, rows, zero_rows ? zero_rows + p0 : nullptr, prm, n2, table + p0, need + p0, slot, on));
-      } else {
-        CorrStorer st{crow, stride, n, pl.w, zero_rows ? zero_rows + p0 : nullptr};
-        PAL_TRY(launch_cols_inv(e, c, G, Wg, st, on));
-      }
+      CorrStorer st{crow, stride, n, pl.w, zero_rows ? zero_rows + p0 : nullptr};
+      PAL_TRY(launch_cols_inv(e, c, G, Wg, st, on));
     }
     if (corr_out && via_scratch)
       PAL_HIP(hipMemcpyAsync(corr_out + size_t(p0) * stride, crow, size_t(rows) * stride * sizeof(double),
                              hipMemcpyDeviceToDevice, on));
-    hipStream_t pon = on;
-    if (split) {
-      PAL_HIP(hipEventRecord(ev_corr[slot], stream));
-      PAL_HIP(hipStreamWaitEvent(stream2, ev_corr[slot], 0));
-      pon = stream2;
-    }
     if (rlean)
-      PAL_TRY(rows_lean_group(pl, crow, stride, G, rows, prm, n2, table + p0, need + p0, slot, pon));
+      PAL_TRY(rows_lean_group(pl, crow, stride, G, rows, prm, n2, table + p0, need + p0, slot, on));
     else if (table && !fused && !fin && !lean)
-      PAL_TRY(peaks(crow, stride, rows, n, n2, prm, table + p0, ksel_multi ? ksel_multi + p0 * PAL_MAX_PEAKS : nullptr, pon));
-    if (split) PAL_HIP(hipEventRecord(ev_peaks[slot], stream2));
+      PAL_TRY(peaks(crow, stride, rows, n, n2, prm, table + p0, ksel_multi ? ksel_multi + p0 * PAL_MAX_PEAKS : nullptr, on));
     return PAL_OK;
   };
   int64_t group = 0;
@@ -652,13 +629,11 @@ int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4
     }
   }
   prof_gate = true;
-  if (two || split) {   // whatever follows on `stream` (downloads, the RCCL gather) sees the finished table
-    PAL_HIP(hipEventRecord(ev_peaks[0], stream2));
-    PAL_HIP(hipStreamWaitEvent(stream, ev_peaks[0], 0));
-    if (nslot == 3) {
-      PAL_HIP(hipEventRecord(ev_join3, stream3));
-      PAL_HIP(hipStreamWaitEvent(stream, ev_join3, 0));
-    }
+  if (nslot == 3) {   // whatever follows on `stream` (downloads, the RCCL gather) sees the finished table
+    PAL_HIP(hipEventRecord(ev_join2, stream2));
+    PAL_HIP(hipStreamWaitEvent(stream, ev_join2, 0));
+    PAL_HIP(hipEventRecord(ev_join3, stream3));
+    PAL_HIP(hipStreamWaitEvent(stream, ev_join3, 0));
   }
   if (fin || lean || rlean) {
     // The pairs the finishing blocks flagged (a threshold comparison inside the median's interval, a tie, a window peak next to

@@ -83,35 +83,27 @@ struct Engine {
   int device = 0;
   int cu_count = 256;              // compute units of the device (persistent kernels size their grids with it)
   hipStream_t stream = nullptr;    // FFT passes, copies, everything a caller can order against
-  hipStream_t stream2 = nullptr;   // second launch-group slot (or the peak selection in PAL_OVERLAP=2)
-  hipStream_t stream3 = nullptr;   // third launch-group slot (PAL_OVERLAP=3)
-  hipEvent_t ev_join3 = nullptr;
+  hipStream_t stream2 = nullptr;   // second and third launch-group slots (pair_correlations; PAL_OVERLAP=0: `stream` only)
+  hipStream_t stream3 = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join2 = nullptr, ev_join3 = nullptr;   // side slots start behind `stream`; `stream` waits for them at the end
   hipEvent_t ev_fin = nullptr;     // end of the latest finishing column pass (pfa_cols_fin.h): they run one at a time, see fin_serialize
   int fin_serialize(hipStream_t on);   // before such a launch: wait for the previous one; fin_done(on) behind it
   int fin_done(hipStream_t on);
   bool fin_pending = false;
   bool fin_serial = false;         // PAL_FIN_SERIAL=1
-  // diagnostic switches of the finishing pass, read when the engine is created (not once per process: tests build engines
-  // under different settings)
-  int fin_dense = -1;              // PAL_FIN_DENSE: 1 / 0 = the pass on every / no dense column DFT; -1 (unset): where it measured faster
-  bool fin_strips = false;         // PAL_FIN_STRIPS=1: also on short columns beside 16384-point row tiles
-  bool fin_four = false;           // PAL_FIN_FOUR=1: on the four-step last pass
-  bool fin_hist = false;           // PAL_FIN_HIST=1: histogram windows for every threshold multiplier
-  bool nohist(const pal_phat_params& prm) const;   // the threshold needs no histograms: 'adaptive', or 'median' with a multiplier in 0 .. 2
+  // switches of the finishing pass, read when the engine is created (not once per process: tests build engines under
+  // different settings)
   bool rows_lean = true;           // PAL_ROWS_LEAN=0: stored rows of the other routes keep the three statistics launches
   long long rows_lean_min = 200000;   // PAL_ROWS_LEAN_MIN=<pairs>: smallest call that takes k_rows_lean (tests lower it)
   bool lean_store = true;          // PAL_LEAN_STORE=0: stored rows keep the round-2 statistics (pfa_cols_stats.h / three launches) + k_peak_finish
   int debug_memo = 0;              // PAL_DEBUG_MEMO=<n>: shrinks the distance rule's on-chip memo / stack (tests of its slow path)
-  hipEvent_t ev_corr[2] = {}, ev_peaks[2] = {};   // hand-offs of the two correlation buffers between the streams
-  int overlap = 3;                 // PAL_OVERLAP: 0 one stream; 1 launch groups alternate between two streams; 2 transforms on
-                                   // `stream`, peak selection on `stream2`; 3 (default) groups rotate over three streams
+  bool one_stream = false;         // PAL_OVERLAP=0: every launch on `stream` (default: launch groups rotate over three streams)
   bool allow_r3 = true;            // PAL_RADIX3=0 forces power-of-two convolution lengths
   bool allow_pfa = true;           // PAL_PFA=0 keeps the PHAT inverse on the four-step chirp convolution
   bool allow_rader = true;         // PAL_RADER=0 keeps the row pass on the in-LDS chirp convolution
   int four_reg = -1;               // PAL_FOUR_REG: register-resident rows of the four-step route: -1 choose, 12 / 13 force 2^12 / 2^13, 0 = LDS tiles only
   bool xcd_rows = true;            // PAL_XCD_ROWS=0: row passes in plain workgroup order (pfa_kernels.h: row_work_item)
   bool allow_big = true;           // PAL_PFA_BIG=0: no register-resident row tiles (N2 <= 2048 only, as in round 1)
-  int pfa_sub = 0;                 // transforms per row/column pass of the prime-factor route (PAL_PFA_SUB; 0 = whole group)
   std::string err;
   static constexpr int kDefaultChunk = 128;
   int chunk = kDefaultChunk;                    // transforms per launch group (forward spectra, simulation, synchronisation)
@@ -196,11 +188,8 @@ struct Engine {
   int peaks_finish(PeakArgs& a, int rows, pal_pair_record* table, int32_t* ksel_multi, hipStream_t on);
   int pfa_rows(const Plan& pl, const cd* permuted, const int4* quads, int G, cd* Y, hipStream_t on);
   bool pfa_can_fuse(const Plan& pl) const;
-  int fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, int grid_cols, const pal_phat_params& prm, int n2, pal_pair_record* table,
+  int fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, const pal_phat_params& prm, int n2, pal_pair_record* table,
                 int* need, int slot, hipStream_t on, PeakArgs& a, struct FinArgs& fa, unsigned& nwg, int G);
-  bool fourstep_can_finish(const Plan& pl, const pal_phat_params& prm) const;   // pfa_cols_fin.h applies to the four-step last pass
-  int fourstep_pair_group_fin(const Plan& pl, const cd* W, int G, int rows, const int* zero_rows, const pal_phat_params& prm, int n2,
-                              pal_pair_record* table, int* need, int slot, hipStream_t on);
   bool pfa_can_finish(const Plan& pl, const pal_phat_params& prm) const;   // pfa_cols_fin.h applies (one peak per row, N1 of 2..4 chunks)
   bool rows_can_lean(const Plan& pl, const pal_phat_params& prm) const;        // k_rows_lean instead of pivots + stream + finish
   int rows_lean_group(const Plan& pl, const double* corr, size_t stride, int G, int rows, const pal_phat_params& prm, int n2,

@@ -285,12 +285,10 @@ int pal_create(int device, pal_handle* out) {
   if ((rc = hipSetDevice(device)) != hipSuccess || (rc = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking)) != hipSuccess ||
       (rc = hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking)) != hipSuccess ||
       (rc = hipStreamCreateWithFlags(&e->stream3, hipStreamNonBlocking)) != hipSuccess ||
+      (rc = hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming)) != hipSuccess ||
+      (rc = hipEventCreateWithFlags(&e->ev_join2, hipEventDisableTiming)) != hipSuccess ||
       (rc = hipEventCreateWithFlags(&e->ev_join3, hipEventDisableTiming)) != hipSuccess ||
-      (rc = hipEventCreateWithFlags(&e->ev_fin, hipEventDisableTiming)) != hipSuccess ||
-      (rc = hipEventCreateWithFlags(&e->ev_corr[0], hipEventDisableTiming)) != hipSuccess ||
-      (rc = hipEventCreateWithFlags(&e->ev_corr[1], hipEventDisableTiming)) != hipSuccess ||
-      (rc = hipEventCreateWithFlags(&e->ev_peaks[0], hipEventDisableTiming)) != hipSuccess ||
-      (rc = hipEventCreateWithFlags(&e->ev_peaks[1], hipEventDisableTiming)) != hipSuccess) {
+      (rc = hipEventCreateWithFlags(&e->ev_fin, hipEventDisableTiming)) != hipSuccess) {
     g_create_error = std::string("device init: ") + hipGetErrorString(rc);
     delete e;
     return PAL_ERR_HIP;
@@ -302,7 +300,7 @@ int pal_create(int device, pal_handle* out) {
   const char* env = getenv("PAL_CHUNK");
   if (env && atoi(env) > 0) { e->chunk = atoi(env); e->chunk_auto = false; }
   env = getenv("PAL_OVERLAP");
-  if (env) e->overlap = atoi(env);
+  e->one_stream = env && atoi(env) == 0;
   env = getenv("PAL_RADIX3");
   if (env) e->allow_r3 = atoi(env) != 0;
   env = getenv("PAL_PFA");
@@ -325,12 +323,6 @@ int pal_create(int device, pal_handle* out) {
   if (env) e->fin_serial = atoi(env) != 0;
   env = getenv("PAL_FIN");
   if (env) e->fin_cols = atoi(env) != 0;
-  env = getenv("PAL_FIN_DENSE");
-  if (env) e->fin_dense = atoi(env) != 0 ? 1 : 0;
-  e->fin_strips = getenv("PAL_FIN_STRIPS") != nullptr;
-  env = getenv("PAL_FIN_FOUR");
-  e->fin_four = env && atoi(env) != 0;
-  e->fin_hist = getenv("PAL_FIN_HIST") != nullptr;
   env = getenv("PAL_ROWS_LEAN");
   if (env) e->rows_lean = atoi(env) != 0;
   env = getenv("PAL_PAIR_BLOCK");
@@ -345,8 +337,6 @@ int pal_create(int device, pal_handle* out) {
   if (env && atoi(env) >= 2) e->fin_wrap = unsigned(atoi(env));
   env = getenv("PAL_DEBUG_FIN_GIVEUP");
   if (env) e->fin_giveup = atoi(env) != 0 ? 1 : 0;
-  env = getenv("PAL_PFA_SUB");
-  if (env) e->pfa_sub = atoi(env);
   env = getenv("PAL_MAX_PLANS");
   if (env && atoi(env) >= 2) e->max_plans = atoi(env);
   *out = reinterpret_cast<pal_handle>(e);
@@ -366,9 +356,10 @@ void pal_destroy(pal_handle h) {
   if (e->quads_blk) hipFree(e->quads_blk);
   if (e->perm_blk) hipFree(e->perm_blk);
   for (hipEvent_t ev : e->ev_pool) hipEventDestroy(ev);
-  for (int k = 0; k < 2; ++k) { hipEventDestroy(e->ev_corr[k]); hipEventDestroy(e->ev_peaks[k]); }
   hipStreamDestroy(e->stream2);
   hipStreamDestroy(e->stream3);
+  hipEventDestroy(e->ev_fork);
+  hipEventDestroy(e->ev_join2);
   hipEventDestroy(e->ev_join3);
   hipEventDestroy(e->ev_fin);
   hipStreamDestroy(e->stream);

@@ -31,11 +31,9 @@
 #include <cfloat>
 #include <climits>
 #include <cmath>
-#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
-#include <vector>
 
 #include "engine.h"
 #include "peak_types.h"
@@ -930,12 +928,6 @@ __device__ __forceinline__ void finish_row(const PeakArgs& a, pal_pair_record* t
   else pre = load_pre(a.pre, row);
   const double k0 = pre.k0, ka = pre.ka, lo = pre.lo, hi = pre.hi;
   const unsigned r1 = unsigned((n - 1) / 2), r2 = unsigned(n / 2);   // ranks of the median's one or two order statistics
-  int stamp_at = 0;
-  auto stamp = [&]() {
-    if (a.stamps && tid == 0) a.stamps[size_t(row) * 8 + stamp_at] = __builtin_amdgcn_s_memrealtime();
-    ++stamp_at;
-  };
-  stamp();
 
   // ---- merge the segments (every lane the same loop: no broadcast needed) ----
   int imax = -1, imin = -1, mb = -1;
@@ -987,7 +979,6 @@ __device__ __forceinline__ void finish_row(const PeakArgs& a, pal_pair_record* t
     below += pt.below;
     if (local) pre.pfloor = fmax(pre.pfloor, pt.pfloor);       // highest bound under which a segment left samples untested
   }
-  stamp();
   if (imax < 0) {                                              // no sample reached the pivot launch's bound for the maximum (insurance): scan
     double bv = 0;
     int bi = -1;
@@ -1092,7 +1083,6 @@ __device__ __forceinline__ void finish_row(const PeakArgs& a, pal_pair_record* t
   if (var < 0) var = 0;
   const double noise = sqrt(var);
   const double snr = noise == 0.0 ? INFINITY : vmax / noise;
-  stamp();
 
   if (a.method < 0) {                                          // metrics only (pal_corr_metrics)
     if (tid == 0) {
@@ -1165,7 +1155,6 @@ __device__ __forceinline__ void finish_row(const PeakArgs& a, pal_pair_record* t
       thi = a.mult >= 0 ? a.mult * mh : a.mult * ml;
     }
   }
-  stamp();
   const bool windowed = !isnan(a.med);
   int wlo = 1, whi = n - 2;
   if (windowed) {
@@ -1269,7 +1258,6 @@ __device__ __forceinline__ void finish_row(const PeakArgs& a, pal_pair_record* t
     if (tid == 0) { s.sel_pos[0] = imax; s.sel_h[0] = vmax; }
     count = 1;
   }
-  stamp();
 
   if (tid == 0) {
     pal_pair_record r;
@@ -1316,7 +1304,6 @@ int Engine::peaks_setup(const double* corr, size_t stride, int rows, int n, int 
   a.snr_w = w > 1 ? w : 1;
   a.edge_n2 = blocks > 0 ? grid_n2 : 0;
   a.local_pivots = blocks > 0 ? 1 : 0;
-  a.stamps = nullptr;
   if (blocks > 0) {
     a.splits = blocks;
     a.tiles_per_seg = 0;
@@ -1359,30 +1346,11 @@ int Engine::peaks_finish(PeakArgs& a, int rows, pal_pair_record* table, int32_t*
   const bool metrics_only = a.method < 0;
   int* status = g_status_dev(this);
   if (!status) return fail(PAL_ERR_NOMEM, "status word");
-  a.stamps = nullptr;
-  static const bool want_stamps = getenv("PAL_DEBUG_STAMPS") != nullptr;
-  if (want_stamps) {
-    void* st = nullptr;
-    PAL_TRY(scratch(13, size_t(rows) * 8 * sizeof(unsigned long long), &st));
-    a.stamps = static_cast<unsigned long long*>(st);
-  }
   {
     ProfScope ps(this, metrics_only ? "k_peak_finish(metrics)" : "k_peak_finish", on);
     if (a.local_pivots) k_peak_finish<true><<<dim3(rows), dim3(kT), 0, on>>>(a, table, ksel_multi, status);
     else k_peak_finish<false><<<dim3(rows), dim3(kT), 0, on>>>(a, table, ksel_multi, status);
     PAL_HIP(hipGetLastError());
-  }
-  if (want_stamps && !metrics_only) {      // diagnostics: median phase times of this launch (synchronises)
-    std::vector<unsigned long long> h(size_t(rows) * 8);
-    PAL_HIP(hipStreamSynchronize(on));
-    PAL_HIP(hipMemcpy(h.data(), a.stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    const char* names[4] = {"merge", "snr window", "threshold", "select"};
-    std::vector<double> d(rows);
-    for (int ph = 0; ph < 4; ++ph) {
-      for (int r = 0; r < rows; ++r) d[r] = double(h[size_t(r) * 8 + ph + 1] - h[size_t(r) * 8 + ph]) / 100.0;
-      std::sort(d.begin(), d.end());
-      fprintf(stderr, "[pal] k_peak_finish %-10s median %6.2f us  p90 %6.2f us  max %6.2f us\n", names[ph], d[rows / 2], d[rows * 9 / 10], d[rows - 1]);
-    }
   }
   return PAL_OK;
 }

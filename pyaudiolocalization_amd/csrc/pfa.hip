@@ -24,10 +24,8 @@
 // bluestein.hip PermSpectrumStorer): row N1-k1
 // is row k1 reversed and conjugated (Hermitian symmetry), so one workgroup serves both rows from the same
 // loads - tile 0 transforms x[k1, e], tile 1 the reversed row z[e] = x[N1-k1, -e], whose DFT is the reversed DFT.
-#include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <utility>
 #include <vector>
 
 #include "pfa_kernels.h"
@@ -372,12 +370,17 @@ int Engine::pfa_pair_group_fused(const Plan& pl, const cd* permuted, const int4*
 
 
 // ---- the column pass that finishes the rows itself (pfa_cols_fin.h, pfa_fin_lean.h): no correlation rows in HBM, no finish launch ----
+
+// the threshold needs no histograms: 'adaptive', or 'median' with a multiplier in 0 .. 2 (pfa_cols_fin.h fin_decide bounds the median)
+static bool nohist(const pal_phat_params& prm) {
+  return prm.threshold_method > 0 || (prm.threshold_multiplier >= 0 && prm.threshold_multiplier <= 2.0);
+}
+
 // One peak per row (main.py:204), the caller does not ask for `corr`, and the grid's rows have at least 256 columns.  Which column
 // forms take it is decided by measurement over the sync-padded lengths (see below); the other plans keep their rows in HBM - with
 // the same per-wavefront statistics where the grid is large enough (pfa_can_lean_store), else with round 2's statistics.
 bool Engine::pfa_can_finish(const Plan& pl, const pal_phat_params& prm) const {
   const Pfa& f = pl.pfa;
-  const bool strips = fin_strips;
   // Measured over L = 44100 ... 44299 with the per-wavefront statistics of pfa_fin_lean.h (profiles/r03_c_length_sweep_dense_fin.csv
   // against ..._default.csv): the pass wins with Rader-89 columns (+10 %), with two or four chunks of output indices (+3 ... +12 %, +4 %)
   // and with short columns beside row tiles of up to 8192 points (+8 %); three chunks leave the fourth wavefront idle (-2 %), and
@@ -388,23 +391,17 @@ bool Engine::pfa_can_finish(const Plan& pl, const pal_phat_params& prm) const {
   // 59 x 407, seven blocks) ran 534 frames/s with the pass and 579 without
   const int nblk = (f.n2 + (f.nch <= 1 ? 4 : 1) * kColsOwn - 1) / ((f.nch <= 1 ? 4 : 1) * kColsOwn);
   if (!f.r89 && nblk < 12) cols_ok = false;
-  if (fin_dense >= 0) cols_ok = f.r89 != nullptr || fin_dense != 0;      // PAL_FIN_DENSE=1 / 0: every / no dense column DFT
-  if (f.nch <= 1 && strips) cols_ok = true;
-  // (five and six chunks, N1 up to 133, are not finished here whatever the switches: pfa_can_fuse stops at four.  Tried with five- /
+  // (five and six chunks, N1 up to 133, are not finished here: pfa_can_fuse stops at four.  Tried with five- /
   // six-wavefront blocks: correct, but C5 ran 2.53 against 2.58 M pairs/s with it - 960 blocks are one round of the machine, every
   // wavefront is in the same phase at the same time and the pass (160 us) is the sum of its latencies, where the separate launches
   // (70 + 18 + 31 + 32) overlap.  Their stored rows take k_rows_lean)
   return fin_cols && pfa_can_fuse(pl) && prm.num_peaks == 1 && f.n2 >= 256 && cols_ok;
 }
 
-bool Engine::nohist(const pal_phat_params& prm) const {
-  return prm.threshold_method > 0 || (prm.threshold_multiplier >= 0 && prm.threshold_multiplier <= 2.0 && !fin_hist);
-}
-
 // The blocks of a finishing pass wait for their siblings (pfa_cols_fin.h).  ONE such launch is deadlock-free (its workgroups are
 // dispatched in order and siblings are adjacent), but two of them on different streams can fill every workgroup slot of the
-// device with blocks that wait for siblings which then find no slot (seen with the four-step source: 34 blocks per transform,
-// two per CU, three streams).  The kernel's waits are bounded and a block that gives up only sends its rows through the
+// device with blocks that wait for siblings which then find no slot (seen with 34 blocks per transform, two per CU, three
+// streams).  The kernel's waits are bounded and a block that gives up only sends its rows through the
 // stored-row path, so this costs time, never correctness.  PAL_FIN_SERIAL=1 runs the finishing launches one at a time
 // instead (each waits for the previous one's end, wherever that ran): no such stall can happen, 10 % slower on the metric run.
 int Engine::fin_serialize(hipStream_t on) {
@@ -418,11 +415,12 @@ int Engine::fin_done(hipStream_t on) {
   return PAL_OK;
 }
 
-// arguments and scratch of one launch of the finishing pass: a grid of `grid_rows` x `grid_cols` samples per row, nblk blocks per transform
-int Engine::fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, int grid_cols, const pal_phat_params& prm, int n2, pal_pair_record* table,
+// arguments and scratch of one launch of the finishing pass, nblk blocks per transform; `grid_rows`: the rows of the grid whose first
+// and last columns go to the finishing wavefront (the prime-factor grid's N1; k_rows_lean has no such columns: 1)
+int Engine::fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, const pal_phat_params& prm, int n2, pal_pair_record* table,
                       int* need, int slot, hipStream_t on, PeakArgs& a, FinArgs& fa, unsigned& nwg, int G) {
   const int n = pl.n;
-  PAL_TRY(peaks_setup(nullptr, 0, rows, n, n2, prm, nblk, grid_cols, on, a));
+  PAL_TRY(peaks_setup(nullptr, 0, rows, n, n2, prm, nblk, 0, on, a));
   // per-stream scratch of the finishing pass: [done words G x blocks | emax | parts | edge] (fin_scratch.h)
   // (`done` words and FinPartial entries: room for one per WAVEFRONT of a block, pfa_fin_lean.h)
   const FinLayout lay = fin_layout(pair_group(n), nblk, grid_rows);
@@ -480,47 +478,7 @@ int Engine::fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, int gri
     }
   }
   fa.cheb = a.method == 0 && nohist(prm) ? 1 : 0;
-  fa.stamps = nullptr;
-  static const bool want_stamps = getenv("PAL_DEBUG_STAMPS") != nullptr;
   nwg = 8u * unsigned((G + 7) / 8) * unsigned(nblk);
-  if (want_stamps) {
-    void* st = nullptr;
-    PAL_TRY(scratch(13, size_t(nwg) * 8 * sizeof(unsigned long long), &st));
-    PAL_HIP(hipMemsetAsync(st, 0, size_t(nwg) * 8 * sizeof(unsigned long long), on));
-    fa.stamps = static_cast<unsigned long long*>(st);
-  }
-  return PAL_OK;
-}
-
-// the last pass of the four-step chirp convolution finishes its rows itself where its columns fit one lane (register rows,
-// M1 <= 24), one peak per row is asked for and the threshold needs no histograms ('adaptive', or 'median' with a multiplier in 0 .. 2)
-bool Engine::fourstep_can_finish(const Plan& pl, const pal_phat_params& prm) const {
-  const Conv& c = pl.inv;
-  const bool off = !fin_four;                                  // opt-in (PAL_FIN_FOUR=1): measured 0.36 against 0.50 M pairs/s for the stored rows + statistics launches
-  return fin_cols && !off && c.reg && c.M1() <= 24 && prm.num_peaks == 1 && nohist(prm) && pl.nout == pl.n;
-}
-
-int Engine::fourstep_pair_group_fin(const Plan& pl, const cd* W, int G, int rows, const int* zero_rows, const pal_phat_params& prm, int n2,
-                                    pal_pair_record* table, int* need, int slot, hipStream_t on) {
-  Engine* e = this;
-  const Conv& c = pl.inv;
-  const int N2 = 1 << c.l2, M1 = c.M1();
-  const int nblk = ((N2 + kColsOwn - 1) / kColsOwn + 3) / 4;
-  PeakArgs a;
-  FinArgs fa;
-  unsigned nwg = 0;
-  PAL_TRY(fin_setup(pl, rows, nblk, M1, N2, prm, n2, table, need, slot, on, a, fa, nwg, G));
-  {
-    char name[48];
-    snprintf(name, sizeof name, "k_colsreg_fin<%d>", M1);
-    ProfScope ps(this, name, on);
-    FinSrc src{W, nullptr, nullptr, c.twA, c.twB, pl.w};
-    fa.pw = 4;                                                 // one FinPartial / `done` word per wavefront (pfa_fin_lean.h)
-    PAL_TRY(fin_serialize(on));
-    PAL_SWITCH_M1(M1, c.l2, k_pfa_cols_fin<kColsFourStep, MM, LR, false, false, 4><<<dim3(nwg), dim3(256), 0, on>>>(src, M1, N2, G, 1, nblk, zero_rows, a, fa, rows));
-    PAL_HIP(hipGetLastError());
-    PAL_TRY(fin_done(on));
-  }
   return PAL_OK;
 }
 
@@ -540,7 +498,7 @@ int Engine::rows_lean_group(const Plan& pl, const double* corr, size_t stride, i
   PeakArgs a;
   FinArgs fa;
   unsigned nwg = 0;
-  PAL_TRY(fin_setup(pl, rows, nblk, 1, kColsOwn, prm, n2, table, need, slot, on, a, fa, nwg, G));
+  PAL_TRY(fin_setup(pl, rows, nblk, 1, prm, n2, table, need, slot, on, a, fa, nwg, G));
   fa.pw = 4;
   fa.corr = const_cast<double*>(corr);
   fa.stride = stride;
@@ -575,11 +533,10 @@ int Engine::pfa_pair_group_fin(const Plan& pl, const cd* permuted, const int4* q
   PeakArgs a;
   FinArgs fa;
   unsigned nwg = 0;
-  PAL_TRY(fin_setup(pl, rows, nblk, f.n1, f.n2, prm, n2, table, need, slot, on, a, fa, nwg, G));
+  PAL_TRY(fin_setup(pl, rows, nblk, f.n1, prm, n2, table, need, slot, on, a, fa, nwg, G));
   fa.corr = corr;
   fa.stride = stride;
   fa.store_rows = corr ? 1 : 0;
-  static const bool want_stamps = getenv("PAL_DEBUG_STAMPS") != nullptr;
   PAL_TRY(pfa_rows(pl, permuted, quads, G, Y, on));
   {
     ProfScope ps(this, corr ? "k_pfa_cols_lean" : "k_pfa_cols_fin", on);
@@ -588,7 +545,7 @@ int Engine::pfa_pair_group_fin(const Plan& pl, const cd* permuted, const int4* q
     // histograms only where the bound sqrt(2 mean(x^2)) on the median cannot decide: multipliers above 2 (or negative)
     const bool hist = !(a.method > 0 || fa.cheb);
     const int nw = f.nch == 2 ? 2 : (f.nch == 3 && !hist ? 3 : 4);   // (three chunks: three wavefronts where the statistics are per wavefront)
-    FinSrc src{Y, f.T, static_cast<const Rader89Tab*>(f.r89), nullptr, nullptr, nullptr};
+    FinSrc src{Y, f.T, static_cast<const Rader89Tab*>(f.r89)};
     PAL_TRY(fin_serialize(on));
 #define PAL_COLS_FIN(MODE, HI, FU, NW) k_pfa_cols_fin<MODE, kPfaTC, kPfaUnr, HI, FU, NW><<<grid, dim3(64 * NW), 0, on>>>(src, f.n1, f.n2, G, f.nch, nblk, zero_rows, a, fa, rows)
 #define PAL_COLS_FIN_FU(MODE, HI, NW) do { if (full) PAL_COLS_FIN(MODE, HI, true, NW); else PAL_COLS_FIN(MODE, HI, false, NW); } while (0)
@@ -602,45 +559,6 @@ int Engine::pfa_pair_group_fin(const Plan& pl, const cd* permuted, const int4* q
 #undef PAL_COLS_FIN
     PAL_HIP(hipGetLastError());
     PAL_TRY(fin_done(on));
-  }
-  if (want_stamps) {                                           // diagnostics: phase times of this launch (synchronises)
-    std::vector<unsigned long long> hst(size_t(nwg) * 8);
-    PAL_HIP(hipStreamSynchronize(on));
-    PAL_HIP(hipMemcpy(hst.data(), fa.stamps, hst.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    const char* names[6] = {"accumulate", "pass A + windows", "pass B + publish", "wait for siblings", "window sums", "finish (last block)"};
-    unsigned long long t0 = ~0ull, t1 = 0;
-    for (unsigned b = 0; b < nwg; ++b)
-      if (hst[size_t(b) * 8]) { t0 = std::min(t0, hst[size_t(b) * 8]); for (int k = 0; k < 7; ++k) t1 = std::max(t1, hst[size_t(b) * 8 + k]); }
-    fprintf(stderr, "[pal] k_pfa_cols_fin: %u workgroups, first start to last stamp %.1f us\n", nwg, double(t1 - t0) / 100.0);
-    {
-      double life = 0;
-      std::vector<std::pair<unsigned long long, int>> ev;
-      for (unsigned b = 0; b < nwg; ++b) {
-        if (!hst[size_t(b) * 8]) continue;
-        unsigned long long e = 0;
-        for (int k = 0; k < 7; ++k) e = std::max(e, hst[size_t(b) * 8 + k]);
-        life += double(e - hst[size_t(b) * 8]) / 100.0;
-        ev.push_back({hst[size_t(b) * 8], 1});
-        ev.push_back({e, -1});
-      }
-      std::sort(ev.begin(), ev.end());
-      int cur = 0, peak = 0;
-      for (auto& x : ev) { cur += x.second; peak = std::max(peak, cur); }
-      fprintf(stderr, "[pal]   resident workgroups: average %.0f, peak %d; mean lifetime %.1f us\n", life / (double(t1 - t0) / 100.0), peak, life / nwg);
-      // when did the workgroups start (index order)?
-      for (unsigned b : {0u, 1u, 8u, 127u, 128u, 767u, 768u, 769u, 1535u, 1536u, 3071u, 3839u})
-        if (b < nwg) fprintf(stderr, "[pal]   workgroup %4u started at %7.1f us, ended at %7.1f\n", b, double(hst[size_t(b) * 8] - t0) / 100.0,
-                             double(std::max(hst[size_t(b) * 8 + 5], hst[size_t(b) * 8 + 6]) - t0) / 100.0);
-    }
-    std::vector<double> d;
-    for (int ph = 0; ph < 6; ++ph) {
-      d.clear();
-      for (unsigned b = 0; b < nwg; ++b)
-        if (hst[size_t(b) * 8 + ph] && hst[size_t(b) * 8 + ph + 1]) d.push_back(double(hst[size_t(b) * 8 + ph + 1] - hst[size_t(b) * 8 + ph]) / 100.0);
-      if (d.empty()) continue;
-      std::sort(d.begin(), d.end());
-      fprintf(stderr, "[pal]   %-20s n %5zu  median %7.2f us  p90 %7.2f us  max %7.2f us\n", names[ph], d.size(), d[d.size() / 2], d[d.size() * 9 / 10], d.back());
-    }
   }
   return PAL_OK;
 }

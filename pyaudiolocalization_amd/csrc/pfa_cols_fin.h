@@ -35,7 +35,8 @@
 // Deadlock freedom of the wait: workgroups are dispatched in index order and the grid index interleaves the eight XCD
 // streams, so the siblings of a block lie within 8 x blocks-per-transform consecutive indices; a waiting block's
 // siblings are resident or next in line, and blocks that do not wait finish on their own.  The spin is bounded anyway
-// (status bit 4 -> PAL_ERR_INTERNAL) so that a violated assumption cannot hang the device.
+// (kSpinLimit below), so that a violated assumption cannot hang the device: a wait that times out flags the transform's
+// rows (need[pair] = 1) and the stored-row path resolves them at the end of the call.
 #pragma once
 #include <climits>
 
@@ -73,7 +74,6 @@ struct FinArgs {
   size_t stride;                  //   has no finishing form): nobody polls siblings then, the finisher reads the SNR window from the stored row
   int store_rows;                 // 1: this pass writes the rows (column forms); 0 with corr set: they are there already (k_rows_lean reads them)
   int cheb;                       // 1: no histograms - the median of |corr| is bounded by sqrt(2 mean(corr^2)) (see fin_decide)
-  unsigned long long* stamps;     // diagnostics (PAL_DEBUG_STAMPS=1): [workgroup][8] 100 MHz clock reads of lane 0 per phase
 };
 
 struct FinWave {                  // one wavefront's share of the finishing block's merge
@@ -412,34 +412,27 @@ __device__ __forceinline__ void fin_row(const PeakArgs& pa, const FinArgs& fa, i
 #include "pfa_fin_lean.h"
 namespace pal {
 
-// Where the samples of a column block come from
-//   kColsDense     prime-factor grid, dense column DFT: the NW wavefronts are chunks of P1 = TC output indices of ONE 62-column strip
-//   kColsRader89   prime-factor grid, N1 = 89: Rader's 8 x 11 convolution spread over four wavefronts (pfa_rader89.h)
-//   kColsStrips    prime-factor grid, short dense column DFT (one chunk, N1 <= 23): the wavefronts are NW neighbouring strips
-//   kColsFourStep  last pass of the four-step chirp convolution with register rows (conv_kernels.h k_colsreg_inv): a lane holds the
-//                  P1 = M1 points of one column of the 2^P2-column workspace, sample m = r 2^P2 + c, the last row is partial
-//                  (m < n); the wavefronts are NW neighbouring strips
-enum { kColsDense = 0, kColsRader89 = 1, kColsStrips = 2, kColsFourStep = 3 };
+// Where the samples of a column block of the prime-factor grid come from
+//   kColsDense     dense column DFT: the NW wavefronts are chunks of TC output indices of ONE 62-column strip
+//   kColsRader89   N1 = 89: Rader's 8 x 11 convolution spread over four wavefronts (pfa_rader89.h)
+//   kColsStrips    short dense column DFT (one chunk, N1 <= 23): the wavefronts are NW neighbouring strips
+enum { kColsDense = 0, kColsRader89 = 1, kColsStrips = 2 };
 
 struct FinSrc {
-  const cd* Y;                    // prime-factor grid [G][N1][N2], or the four-step workspace [G][M1][2^LR]
+  const cd* Y;                    // prime-factor grid [G][N1][N2]
   const double* T;                // dense column DFT: cos / sin table (pfa_kernels.h)
   const Rader89Tab* tab;          // kColsRader89
-  const cd *twA, *twB, *w;        // kColsFourStep: root tables of the convolution, chirp exp(i pi j^2 / n)
 };
 
 // grid: 8 * ceil(G / 8) * nblk workgroups; index b -> XCD stream b & 7, slot b >> 3; the transforms g = x, x + 8, ... of stream x
 // take nblk consecutive slots each (siblings adjacent, one XCD's L2 behind them when G is a multiple of 8)
 // HIST: threshold method 'median' with a histogram window per block (a rigorous 0.5 % interval for the row's median); false:
 //       'adaptive', or 'median' bounded without histograms (FinArgs.cheb: multipliers up to 2)
-template <int MODE, int P1, int P2, bool HIST, bool FULL, int NW>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE == kColsRader89 || (MODE == kColsFourStep && P1 <= 16) ? 3 : 2))) void k_pfa_cols_fin(FinSrc src, int N1, int N2, int G, int nch, int nblk,
+template <int MODE, int TC, int UNR, bool HIST, bool FULL, int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE == kColsRader89 ? 3 : 2))) void k_pfa_cols_fin(FinSrc src, int N1, int N2, int G, int nch, int nblk,
                                                       const int* __restrict__ zero_rows, PeakArgs pa, FinArgs fa, int rows) {
-  constexpr bool R89 = MODE == kColsRader89, FOUR = MODE == kColsFourStep;
-  constexpr bool STRIPS = MODE == kColsStrips || MODE == kColsFourStep;
-  constexpr int TC = FOUR ? 1 : P1, UNR = FOUR ? 1 : P2;
+  constexpr bool R89 = MODE == kColsRader89, STRIPS = MODE == kColsStrips;
   static_assert(!R89 || (NW == 4 && FULL), "the Rader column transform is the four-wavefront N1 = 89 case");
-  static_assert(!FOUR || !HIST, "the four-step last pass finishes its rows without histograms only");
   static_assert(!HIST || NW <= 4, "the histogram form merges at most four wavefronts per block");
   const cd* __restrict__ Y = src.Y;
   const double* __restrict__ T = src.T;
@@ -461,12 +454,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
   const int xs = int(blockIdx.x & 7u), slot = int(blockIdx.x >> 3);
   const int cb = slot % nblk, g = xs + 8 * (slot / nblk);
   if (g >= G) return;                                          // (uniform: the grid is padded to whole XCD rounds)
-  int stamp_at = 0;
-  auto stamp = [&]() {
-    if (fa.stamps && tid == 0) fa.stamps[size_t(blockIdx.x) * 8 + stamp_at] = __builtin_amdgcn_s_memrealtime();
-    ++stamp_at;
-  };
-  stamp();
   // the grid's columns are dealt evenly to the strips (at most kColsOwn = 62 each: two border lanes per wavefront)
   const int strips = STRIPS ? nblk * NW : nblk, strip = STRIPS ? cb * NW + wave : cb;
   const int nact = STRIPS ? NW : nch;                          // wavefronts of a block that hold samples
@@ -485,15 +472,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
     unsigned* hz = &hist[0][0];
     for (int q = tid; q < 2 * (kLogBins + 1); q += LANES) hz[q] = 0;
   }
-  constexpr int TCD = (R89 || FOUR) ? 1 : TC;                  // (the dense form's accumulators exist in the dense forms only)
+  constexpr int TCD = R89 ? 1 : TC;                            // (the dense form's accumulators exist in the dense forms only)
   double cx[TCD], sy[TCD], cy[TCD], sx[TCD];
   double sumx = 0, sumy = 0;
   cd y0 = mk(0, 0);
-  cd ro[R89 ? kR89Slots : (FOUR ? P1 : 1)];                    // Rader form: c[t] of the output indices tab->tmap[wave][.]; four-step: the column's P1 points
+  cd ro[R89 ? kR89Slots : 1];                                  // Rader form: c[t] of the output indices tab->tmap[wave][.]
   cd c0 = mk(0, 0);                                            // Rader form: c[0] (wavefront 0)
   const double kp = zero_rows && zero_rows[2 * g] ? 0.0 : 1.0, kq = zero_rows && 2 * g + 1 < rows && zero_rows[2 * g + 1] ? 0.0 : 1.0;
-  // four-step: does sample (t, this lane's column) exist?  (the last row of the workspace's grid is partial: m = t N2 + m2 < n)
-  auto ok_at = [&](int t) { return !FOUR || t * N2 + m2 < n; };
   // Rader form: the output index of slot i sits in lane i of one register (loaded once; a scalar load per sample and pass made
   // every statistics loop a chain of scalar-memory latencies - 140 of them per wavefront)
   int slot_t = 0;
@@ -509,19 +494,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
 #pragma unroll
       for (int i = 0; i < kR89Slots; ++i) { ro[i].x *= kp; ro[i].y *= kq; }
     }
-  } else if constexpr (FOUR) {
-    // conv_kernels.h k_colsreg_inv: the column's M1 points, four-step twiddle, inverse M1-point DFT, then the chirp (bluestein.hip CorrStorer)
-    const cd* in = Y + (size_t(g) * P1 << P2) + m2c;
-#pragma unroll
-    for (int k1 = 0; k1 < P1; ++k1) ro[k1] = in[size_t(k1) << P2];
-    colsreg_twiddle<P1, P2, true>(ro, unsigned(m2c), src.twA, src.twB);
-    reg_dft<P1, true>(ro, src.twA);
-#pragma unroll
-    for (int r = 0; r < P1; ++r) {
-      const int j = (r << P2) + m2c;
-      const cd z = j < n ? cmul(ro[r], src.w[j]) : mk(0, 0);
-      ro[r] = mk(z.x * kp, z.y * kq);
-    }
   } else {
     if (active) pfa_cols_accumulate<TC, UNR>(Y + size_t(g) * N1 * N2 + m2c, N1, N2, nch, ch, T, y0, cx, sy, cy, sx, sumx, sumy);
     if (kp == 0.0) { y0.x = sumx = 0.0; }
@@ -531,22 +503,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
       cx[tt] *= kp; sy[tt] *= kp; cy[tt] *= kq; sx[tt] *= kq;
     }
   }
-  stamp();                                                     // 1: accumulated
   if constexpr (!HIST) {
     // every wavefront on its own from here (pfa_fin_lean.h); ONE wavefront of the transform's last block then finishes both rows
     bool last;
     if constexpr (R89) {
       last = fin_lean_r89<true, false, kR89Slots>(ro, c0, slot_t, 0u, wave, lane, g, cb, nblk, N1, N2, rows, c_lo, m2, own, inner, cb == 0 || cb == nblk - 1,
-                                                  -1, true, pa, fa, stamp);
-    } else if constexpr (FOUR) {
-      // four-step workspace: slot 1 + r = grid row r (t = r), no slot 0; the row ends inside grid row (n - 1) / N2
-      unsigned emask = 0;
-#pragma unroll
-      for (int r = 0; r < P1; ++r)
-        if (r * N2 < n) emask |= 1u << (1 + r);
-      const int pr = (n - 1) / N2;
-      last = fin_lean_r89<false, true, P1>(ro, mk(0, 0), lane, emask, wave, lane, g, cb, nblk, N1, N2, rows, c_lo, m2, own, inner, c_lo == 0 || c_hi == N2,
-                                           1 + pr, pr * N2 + m2 < n, pa, fa, stamp);
+                                                  -1, true, pa, fa);
     } else {
       // dense column DFT: the accumulators become samples once (slot 1 + tt: t = ch TC + tt + 1, slot 1 + TC + tt: N1 - t; slot 0: t = 0)
       static_assert(R89 || 2 * TCD == kR89Slots, "22 slots per wavefront");
@@ -562,22 +524,18 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
       const int tl = ch * TC + (lane < TCD ? lane : lane - TCD) + 1;
       const int st = lane < TCD ? tl : N1 - tl;
       last = fin_lean_r89<false, false, kR89Slots>(zs, z0, st, emask, wave, lane, g, cb, nblk, N1, N2, rows, c_lo, m2, own, inner,
-                                                   active && (c_lo == 0 || c_hi == N2), -1, true, pa, fa, stamp);
+                                                   active && (c_lo == 0 || c_hi == N2), -1, true, pa, fa);
     }
     if (!last) return;
-    stamp();                                                   // 5
     if (wave != 0) return;                                     // ONE wavefront finishes the transform's rows (fin_row_wave)
-    fin_rows_wave(pa, fa, g, nblk, rows, N1, N2, lane, stamp);
+    fin_rows_wave(pa, fa, g, nblk, rows, N1, N2, lane);
     return;
   }
   // the samples of this lane, fn(value, t, exists): `value()` yields the sample (formed by two additions in the dense form, so
   // only where it is wanted); t and `exists` are wave-uniform.  Dense form: lag order (t = 0 for chunk 0 only, the chunk
   // ascending, the mirrors descending); Rader form: table order
   auto each_sample = [&](int r, auto&& fn) {
-    if constexpr (FOUR) {
-#pragma unroll
-      for (int i = 0; i < P1; ++i) fn([&]() { return r ? ro[i].y : ro[i].x; }, i, i * N2 < n);
-    } else if constexpr (R89) {
+    if constexpr (R89) {
       fn([&]() { return r ? c0.y : c0.x; }, 0, wave == 0);
 #pragma unroll
       for (int i = 0; i < kR89Slots; ++i) fn([&]() { return r ? ro[i].y : ro[i].x; }, __builtin_amdgcn_readlane(slot_t, i), true);
@@ -611,13 +569,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
       char* const hrow = reinterpret_cast<char*>(&hist[r][0]);
       each_sample(r, [&](auto&& value, int t, bool exists) {
         if (!exists) return;
-        const double xv = value();
-        const bool ok = ok_at(t);                              // (four-step: the last grid row is partial)
-        const double x = ok ? xv : 0.0;
-        const bool up = ok & ((x > vm) | (R89 & (x == vm) & (t < tm)));  // (Rader form: not in lag order - the smaller index of equal samples; no short cuts: one basic block)
+        const double x = value();
+        const bool up = (x > vm) | (R89 & (x == vm) & (t < tm));   // (Rader form: not in lag order - the smaller index of equal samples; no short cuts: one basic block)
         vm = up ? x : vm;
         tm = up ? t : tm;
-        vn = ok ? min_raw(vn, x) : vn;
+        vn = min_raw(vn, x);
         s1 += x;
         s2 = __builtin_fma(x, x, s2);
         a1 += fabs(x);
@@ -705,11 +661,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
       each_sample(r, [&](auto&& value, int t, bool exists) {
         if (!exists) return;
         const double x = value();
-        if (mine && ok_at(t)) st_agent(dst + t, x);
+        if (mine) st_agent(dst + t, x);
       });
     }
   }
-  stamp();                                                     // 2: pass A, histogram windows, edge columns
 
   // ---- pass B: the highest strict peak behind the block's exact bound; a block whose bounded search found no peak
   //      searches all its samples (second round), so its result is exact
@@ -740,12 +695,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
           if (__ballot(x >= myfloor)) {
             const int m = m2 + N2 * t;
             const double left = from_lower_lane(x), right = from_upper_lane(x);
-            const bool here = inner && (!FOUR || m <= n - 2);    // (four-step: the row ends inside the grid's last row)
-            const bool cand = here && x >= pfloor && (R89 ? (x > hb || (x == hb && m > mb)) : x >= hb);
+            const bool cand = inner && x >= pfloor && (R89 ? (x > hb || (x == hb && m > mb)) : x >= hb);
             const bool pk = cand && left < x && right < x;
             hb = pk ? x : hb;
             mb = pk ? m : mb;
-            plat = here && x >= pfloor && left == x ? fmax(plat, x) : plat;
+            plat = inner && x >= pfloor && left == x ? fmax(plat, x) : plat;
           }
         });
       }
@@ -800,7 +754,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
     __syncthreads();
   }
   // ---- phase 2: the siblings' maxima (published long ago), then the SNR window sums of this block's samples
-  stamp();                                                     // 3: pass B
   if (tid == 0) s_flag = 0;                                    // (1: a wavefront gave up waiting for the siblings' maxima)
   __syncthreads();
   if (wave < 2 && 2 * g + wave < rows) {
@@ -829,7 +782,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
     if (lane == 63) s_imax[wave] = bi;
   }
   __syncthreads();
-  stamp();                                                     // 4: the row's argmax is known
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
     if (2 * g + r >= rows) continue;
@@ -843,7 +795,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
       each_sample(r, [&](auto&& value, int t, bool exists) {
         if (!exists || t < tA || t > tB) return;               // (uniform)
         const double x = value();
-        const bool in = own && (t > tA || inA) && (t < tB || inB) && ok_at(t);
+        const bool in = own && (t > tA || inA) && (t < tB || inB);
         const double xm = in ? x : 0.0;
         w1 += xm;
         w2 = __builtin_fma(xm, xm, w2);
@@ -880,7 +832,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
   stores_done();                                               // this wavefront's stores (results, histogram windows, edge columns) have landed ...
   __syncthreads();                                             // ... and so have the other wavefronts' before lane 0 announces the block
   if (tid == 0) st_agent(fa.done + size_t(g) * nblk + cb, fa.epoch);
-  stamp();                                                     // 5: published
   if (cb != nblk - 1) return;                                  // (uniform)
 
   // ---- the last block of the transform waits for its siblings' results and finishes both rows
@@ -902,12 +853,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
 #pragma nounroll
   for (int r = 0; r < 2; ++r)
     if (2 * g + r < rows) fin_row<LANES>(pa, fa, 2 * g + r, N1, N2, nact, fsh, tid);
-  stamp();                                                     // 6: both rows finished (last block only)
 }
 
 
-// ---- per-wavefront statistics over rows that are already in HBM (any route: the four-step last pass, column DFTs of five or six
-//      chunks, small grids): the counterpart of k_peak_pivots + k_peak_stream + k_peak_finish for one peak per row without histograms.
+// ---- per-wavefront statistics over rows that are already in HBM (any route: the four-step chirp convolution, column DFTs of five or
+//      six chunks, small grids): the counterpart of k_peak_pivots + k_peak_stream + k_peak_finish for one peak per row without histograms.
 // A wavefront reads NS overlapping chunks of 64 consecutive samples of both rows of a transform - chunk t = samples 62 t - 1 ...
 // 62 t + 62: lanes 1 .. 62 own a sample, lanes 0 and 63 hold the neighbours - which is the (slot, lane) layout of pfa_fin_lean.h with
 // N2 = 62 columns, m = 62 t + (lane - 1): the row's partial last chunk is the PART slot, chunks behind it do not exist.  No sibling
@@ -919,12 +869,6 @@ __global__ __launch_bounds__(256) void k_rows_lean(const double* __restrict__ co
   const int xs = int(blockIdx.x & 7u), slot = int(blockIdx.x >> 3);
   const int cb = slot % nblk, g = xs + 8 * (slot / nblk);
   if (g >= G) return;                                          // (uniform)
-  int stamp_at = 0;
-  auto stamp = [&]() {
-    if (fa.stamps && tid == 0) fa.stamps[size_t(blockIdx.x) * 8 + stamp_at] = __builtin_amdgcn_s_memrealtime();
-    ++stamp_at;
-  };
-  stamp();
   constexpr int W = kColsOwn;                                  // 62 owned samples per chunk
   const int n = pa.n;
   const int t0 = (cb * 4 + wave) * NS;                         // first chunk of this wavefront
@@ -942,18 +886,16 @@ __global__ __launch_bounds__(256) void k_rows_lean(const double* __restrict__ co
     ro[i] = mk(ok ? a : 0.0, ok ? b * keep1 : 0.0);
     if (W * (t0 + i) < n) emask |= 1u << (1 + i);
   }
-  stamp();                                                     // 1: loaded
   const int tp = (n - 1) / W;                                  // the row ends inside chunk tp
   const int pslot = tp >= t0 && tp < t0 + NS ? 1 + tp - t0 : -1;
   const bool own = lane >= 1 && lane <= W;
   const bool pvalid = W * tp + lane - 1 < n;
   const int st = t0 + (lane < NS ? lane : 0);
   const bool last = fin_lean_r89<false, true, NS>(ro, mk(0, 0), st, emask, wave, lane, g, cb, nblk, 0, W, rows, 0, lane - 1, own, own, false, pslot,
-                                                  pvalid, pa, fa, stamp);
+                                                  pvalid, pa, fa);
   if (!last) return;
-  stamp();                                                     // 5
   if (wave != 0) return;                                       // ONE wavefront finishes the transform's rows
-  fin_rows_wave(pa, fa, g, nblk, rows, 0, W, lane, stamp);
+  fin_rows_wave(pa, fa, g, nblk, rows, 0, W, lane);
 }
 
 }  // namespace pal

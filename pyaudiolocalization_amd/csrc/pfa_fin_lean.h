@@ -112,13 +112,14 @@ __device__ __forceinline__ double wave_pair_min(double a, double b) { return wav
 // General form (dense column DFTs, strips): `emask` bit s = slot s exists (slot 0 = c0; ALL: every slot 1 .. 22 exists and slot 0 in
 // wavefront 0 only - the Rader-89 case); `edge_block`: the wavefront's columns touch the grid's first or last column; the
 // wavefront's entries sit at index (cb, wave) of fa.pw per block.
-// PART (the four-step workspace, sample m = N2 t + m2 < n): the row ends inside slot `pslot` - its samples are valid where `pvalid`
-// (the others hold zeros, which the sums may see but maxima, minima and the index search must not), later slots do not exist.
-template <bool ALL, bool PART, int NS, class STAMP>
+// PART (k_rows_lean's chunks of a stored row, sample m = N2 t + m2 < n): the row ends inside slot `pslot` - its samples are valid
+// where `pvalid` (the others hold zeros, which the sums may see but maxima, minima and the index search must not), later slots do
+// not exist.
+template <bool ALL, bool PART, int NS>
 __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, const int slot_t, const unsigned emask, const int wave, const int lane,
                                              const int g, const int cb, const int nblk, const int N1, const int N2, const int rows, const int c_lo,
                                              const int m2, const bool own, const bool inner, const bool edge_block, const int pslot, const bool pvalid,
-                                             const PeakArgs& pa, const FinArgs& fa, STAMP&& stamp) {
+                                             const PeakArgs& pa, const FinArgs& fa) {
   static_assert(NS + 1 <= 32, "slot masks are 32 bits");
   const int n = pa.n, S = pa.splits, PW = fa.pw;
   const unsigned long long pvm = PART ? __ballot(pvalid) : ~0ull;
@@ -206,7 +207,7 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
           if (__ballot(x >= myfloor)) {
             const int m = m2 + N2 * T(slot);
             const double left = from_lower_lane(x), right = from_upper_lane(x);
-            const bool here = inner && (!PART || (m >= 1 && m <= n - 2));   // (the row's end points are never peaks; four-step / row chunks: the row ends inside a slot)
+            const bool here = inner && (!PART || (m >= 1 && m <= n - 2));   // (the row's end points are never peaks; row chunks: the row ends inside a slot)
             const bool cand = here && x >= pfloor && (x > hb || (x == hb && m > mb));
             const bool pk = cand && left < x && right < x;
             hb = pk ? x : hb;
@@ -241,7 +242,6 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
       pt[r].platw = uniform_max_sparse(platw);
     }
   }
-  stamp();                                                     // 2: passes A and B
 
   // ---- the grid's edge columns go to the finishing block as they are (blocks 0 and nblk - 1 only)
   if (edge_block) {                                            // (uniform)
@@ -326,7 +326,6 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
     w1[r] = u1; w2[r] = u2;
   }
   if (gave_up && lane == 0) atomicAdd(fa.status + 13, 1);
-  stamp();                                                     // 3: the row's argmax, window sums
 
   // ---- the window sums' butterfly; lane r publishes row r's results, then the wavefront's `done` word follows
   {
@@ -345,7 +344,6 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
   }
   stores_done();                                               // this wavefront's stores (results, edge columns) have landed
   if (lane == 0) st_agent(fa.done + (size_t(g) * nblk + cb) * PW + wave, fa.epoch);
-  stamp();                                                     // 4: published
   return cb == nblk - 1;
 }
 
@@ -431,10 +429,8 @@ __device__ __forceinline__ void fin_row_wave(const PeakArgs& pa, const FinArgs& 
 }
 
 // ---- the tail of a per-wavefront pass, in wavefront 0 of the transform's last block: wait for every wavefront's `done` word, then
-//      finish rows 2 g and 2 g + 1 and take the kernel's stamp 6.  When the siblings' results are not there in time both rows go through
-//      the stored-row path instead
-template <class STAMP>
-__device__ __forceinline__ void fin_rows_wave(const PeakArgs& pa, const FinArgs& fa, int g, int nblk, int rows, int N1, int N2, int lane, STAMP&& stamp) {
+//      finish rows 2 g and 2 g + 1.  When the siblings' results are not there in time both rows go through the stored-row path instead
+__device__ __forceinline__ void fin_rows_wave(const PeakArgs& pa, const FinArgs& fa, int g, int nblk, int rows, int N1, int N2, int lane) {
   bool late = fa.giveup != 0;                                  // (PAL_DEBUG_FIN_GIVEUP=1: no polls, both rows flagged)
   for (int q = lane; !fa.giveup && q < nblk * fa.pw; q += 64) {
     int spins = 0;
@@ -450,7 +446,6 @@ __device__ __forceinline__ void fin_rows_wave(const PeakArgs& pa, const FinArgs&
 #pragma nounroll
   for (int r = 0; r < 2; ++r)
     if (2 * g + r < rows) fin_row_wave(pa, fa, 2 * g + r, N1, N2, lane);
-  stamp();                                                     // 6: both rows finished (last block only)
 }
 
 }  // namespace pal

@@ -14,14 +14,15 @@ static int failures = 0;
 
 // The forms of the finishing pass at 44.1 kHz (tests/test_gpu_parity.py FIN_CASES), from the plans' N1 x N2 (pal_plan_info /
 // pal_plan_factors): nblk = ceil(N2 / 62) column blocks (kColsOwn), ceil(N2 / 248) for one-chunk strips (N1 <= 23); the grid has N1
-// rows.  The four-step pass (L = 44101: 22 x 8192 points) has ceil(ceil(8192 / 62) / 4) = 34 blocks and M1 = 22 rows.
+// rows.  The last entry is the layout of a removed form (the four-step last pass at L = 44101: 34 blocks, 22 rows), kept as one more
+// geometry for the reset rule.
 struct Form { int L, nblk, grid_rows; };
 static const Form kForms[] = {{44100, 16, 89},    // 89 x 991, Rader-89 columns
                               {44113, 57, 25},    // 25 x 3529
                               {44110, 31, 47},    // 47 x 1877
                               {44254, 22, 67},    // 67 x 1321
                               {44103, 16, 23},    // 23 x 3835, strips
-                              {44101, 34, 22}};   // four-step last pass
+                              {44101, 34, 22}};   // a 34-block, 22-row layout (once the four-step last pass)
 static const int kGroups[] = {240, 32};           // the automatic group size at 44.1 kHz, and pal_set_chunk(32)
 
 struct Geo { int L, gmax, nblk, grid_rows; FinLayout lay; };

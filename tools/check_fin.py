@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of the finishing column pass (PAL_FIN=1, pfa_cols_fin.h) against the stored-row path (PAL_FIN=0) on one box:
 every record field of random and structured frames, both window modes, both threshold methods.
-    python tools/check_fin.py [mics] [frames] [length=44100]     (PAL_FIN_DENSE=1 / PAL_FIN_STRIPS=1: the pass on dense column DFTs)"""
+    python tools/check_fin.py [mics] [frames] [length=44100]"""
 import os
 import sys
 

@@ -93,9 +93,12 @@ def speed():
     frames = metric_frames(1, 64)
     prm = make_params(44100, 1, "median", 1.0, 0.05)
     ref = None
-    for overlap in (1, 0):
+    for overlap in ("default", "0"):                            # three rotating stream slots, one stream
         for chunk in (16, 32, 64, 128):
-            os.environ["PAL_OVERLAP"] = str(overlap)
+            if overlap == "0":
+                os.environ["PAL_OVERLAP"] = "0"
+            else:
+                os.environ.pop("PAL_OVERLAP", None)
             e2 = Engine(0)
             e2.set_chunk(chunk)
             d_f = e2.alloc(frames.nbytes); e2.upload(d_f, frames)

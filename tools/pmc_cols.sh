@@ -6,12 +6,11 @@ ROOT=$GRAFT_REPO_ROOT
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-export STAMPS=0
 for fin in ${FINS:-1 0}; do
   export PAL_FIN=$fin
   for pass in "a SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES" "b SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU" "c SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_INSTS_VALU_FMA_F64 SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INST_CYCLES_SALU"; do
     set -- $pass; name=$1; shift
-    timeout -k 10 200 rocprofv3 --kernel-trace --pmc "$@" -d $OUT/fin$fin/$name -o $name --output-format csv -- python3 $ROOT/tools/stamps_fin.py > $OUT/fin${fin}_$name.log 2>&1 || echo "pass $fin $name failed"
+    timeout -k 10 200 rocprofv3 --kernel-trace --pmc "$@" -d $OUT/fin$fin/$name -o $name --output-format csv -- python3 $ROOT/tools/fin_workload.py > $OUT/fin${fin}_$name.log 2>&1 || echo "pass $fin $name failed"
   done
 done
 python3 - <<PY

@@ -6,10 +6,9 @@ ROOT=$GRAFT_REPO_ROOT
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-export STAMPS=0
 for v in "$@"; do
   if [ $v = base ]; then unset PAL_LIB_PATH; else export PAL_LIB_PATH=$ROOT/tools/bin/libpal_$v.so; fi
-  timeout -k 10 200 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU -d $OUT/$v -o p --output-format csv -- python3 $ROOT/tools/stamps_fin.py > $OUT/$v.log 2>&1 || echo "$v failed"
+  timeout -k 10 200 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU -d $OUT/$v -o p --output-format csv -- python3 $ROOT/tools/fin_workload.py > $OUT/$v.log 2>&1 || echo "$v failed"
 done
 python3 - <<PY
 import csv, glob, collections

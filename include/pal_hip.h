@@ -131,6 +131,29 @@ int pal_gcc_phat_pairs(pal_handle h, const double* rows, int R, int L, const int
 int pal_gcc_phat_pairs_dev(pal_handle h, const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P,
                            const pal_phat_params* prm, pal_pair_record* d_table);
 
+/* ---- bootstrap significance (utils.py:183-216) on the device -------------------------------
+ * The reference shuffles sig2 = row j from NumPy's global RNG 1000 times per pair and keeps the (1 - alpha) percentile of
+ * max(PHAT(sig1, shuffled sig2)).  Here shuffle s of pair (i, j) is a pure function of (seed, i, j, s, L, mode, block_size):
+ * a counter-based generator in exact 64-bit integer arithmetic (pyaudiolocalization_amd/bootstrap.py restates it bit for
+ * bit).  It is keyed on the row indices of the pair, so the results are keyed per pair: they do not depend on the order of
+ * the pair list, on which other pairs are listed, or on how the shuffles are cut into rounds (pal_set_chunk).  Statistically
+ * equivalent to the reference's shuffles, not bitwise equal to them.
+ *   permutation: a keyed bijection of [0, L);  block: the blocks of block_size samples in keyed order, the short last block
+ *   keeping its length;  circular: np.roll(row, shift) with a keyed shift in [0, L).
+ * Invalid mode, block_size < 1, num_bootstrap (S) < 1 or a row index outside 0..R-1: PAL_ERR_INVALID (the _dev form reports a
+ * bad row index of its device pair list through pal_synchronize).  Non-finite samples: as the batched calls above. */
+#define PAL_BOOT_PERMUTATION 0
+#define PAL_BOOT_BLOCK 1
+#define PAL_BOOT_CIRCULAR 2
+/* shuffles s0 .. s0+S-1 of row d_row[L] under the key (seed, i, j): d_out[S][L] */
+int pal_bootstrap_shuffle_dev(pal_handle h, const double* d_row, int L, int32_t i, int32_t j, int32_t mode, int32_t block_size,
+                              uint64_t seed, int64_t s0, int32_t S, double* d_out);
+/* peaks[P][S] = max PHAT(rows[i], shuffle s of rows[j]) for every listed pair (i, j) */
+int pal_bootstrap_peaks(pal_handle h, const double* rows, int R, int L, const int32_t* pairs, int64_t P, int32_t num_bootstrap,
+                        int32_t mode, int32_t block_size, uint64_t seed, double* peaks);
+int pal_bootstrap_peaks_dev(pal_handle h, const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P,
+                            int32_t num_bootstrap, int32_t mode, int32_t block_size, uint64_t seed, double* d_peaks);
+
 /* single-pair signatures: phat_correlation(sig1, sig2) (utils.py:108) -> corr[n1+n2-1] */
 int pal_phat_correlation(pal_handle h, const double* sig1, int n1, const double* sig2, int n2, double* corr);
 /* get_time_delays_phat (utils.py:121): corr[n1+n2-1] (may be NULL), k_out[num_peaks] array indices */

@@ -124,7 +124,8 @@ struct Engine {
   cd* stage_tw[16] = {};                        // stage-major twiddles per log2 N (<= 14: the big row tiles of pfa_big.h)
   cd* stage_twc[16] = {};                       // the same with a compact last stage (fft_core.h stage_twc_size)
   // growable device scratch
-  void* ws[24] = {};              // (16..18: per-stream scratch of the finishing column pass, pfa_cols_fin.h; 19..21: its flagged pairs)
+  void* ws[24] = {};              // (16..18: per-stream scratch of the finishing column pass, pfa_cols_fin.h; 19..21: its flagged pairs;
+                                  //  8, 9, 12: per-stream peak selection, peaks.hip; 10, 11, 13: the bootstrap's shuffled rows, round tables, host-call peaks)
   size_t ws_bytes[24] = {};
   // profiling
   bool profiling = false;
@@ -178,6 +179,12 @@ struct Engine {
                         const int* nonzero = nullptr);
   int pairs_dev(const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P, const pal_phat_params& prm,
                 pal_pair_record* d_table);
+  // bootstrap.hip: counter-based shuffles (pal_bootstrap_shuffle_dev) and the shuffled pairs through the pair pipeline, round by round
+  int bootstrap_shuffle_dev(const double* d_row, int L, int32_t i, int32_t j, int32_t mode, int32_t block_size, uint64_t seed, int64_t s0,
+                            int32_t S, double* d_out);
+  int bootstrap_round(const Plan& pl, int L) const;   // shuffled rows per round
+  int bootstrap_peaks_dev(const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P, int32_t S, int32_t mode, int32_t block_size,
+                          uint64_t seed, double* d_peaks);
   int peaks(const double* corr, size_t stride, int rows, int n, int n2, const pal_phat_params& prm,
             pal_pair_record* table, int32_t* ksel_multi, hipStream_t on);
   // the same in pieces, for the column pass that produces the streaming statistics itself (pfa_cols_stats.h):

@@ -477,6 +477,42 @@ int pal_gcc_phat_pairs_dev(pal_handle h, const double* d_rows, int R, int L, con
   return e->pairs_dev(d_rows, R, L, d_pairs, P, *prm, d_table);
 }
 
+int pal_bootstrap_shuffle_dev(pal_handle h, const double* d_row, int L, int32_t i, int32_t j, int32_t mode, int32_t block_size,
+                              uint64_t seed, int64_t s0, int32_t S, double* d_out) {
+  ENGINE(h);
+  if (!d_row || !d_out) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  return e->bootstrap_shuffle_dev(d_row, L, i, j, mode, block_size, seed, s0, S, d_out);
+}
+
+int pal_bootstrap_peaks_dev(pal_handle h, const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P,
+                            int32_t num_bootstrap, int32_t mode, int32_t block_size, uint64_t seed, double* d_peaks) {
+  ENGINE(h);
+  if (!d_rows || !d_pairs || !d_peaks) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  return e->bootstrap_peaks_dev(d_rows, R, L, d_pairs, P, num_bootstrap, mode, block_size, seed, d_peaks);
+}
+
+int pal_bootstrap_peaks(pal_handle h, const double* rows, int R, int L, const int32_t* pairs, int64_t P, int32_t num_bootstrap,
+                        int32_t mode, int32_t block_size, uint64_t seed, double* peaks) {
+  ENGINE(h);
+  if (!rows || !pairs || !peaks) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  if (R < 1 || L < 1 || P < 1) return e->fail(PAL_ERR_INVALID, "need R >= 1, L >= 1, P >= 1");
+  if (num_bootstrap < 1) return e->fail(PAL_ERR_INVALID, "num_bootstrap must be at least 1");
+  if (P > (int64_t(1) << 40) / num_bootstrap) return e->fail(PAL_ERR_UNSUPPORTED, "too many pairs x shuffles");
+  for (int64_t k = 0; k < 2 * P; ++k)
+    if (pairs[k] < 0 || pairs[k] >= R) return e->fail(PAL_ERR_INVALID, "pair %lld references row outside 0..%d", (long long)(k / 2), R - 1);
+  const size_t pbytes = size_t(P) * size_t(num_bootstrap) * sizeof(double);
+  void *df = nullptr, *dp = nullptr, *dk = nullptr;
+  PAL_TRY(e->scratch(4, size_t(R) * L * sizeof(double), &df));
+  PAL_TRY(e->scratch(15, size_t(2 * P) * sizeof(int32_t), &dp));
+  PAL_TRY(e->scratch(13, pbytes, &dk));
+  PAL_TRY(e->check(hipMemcpyAsync(df, rows, size_t(R) * L * sizeof(double), hipMemcpyHostToDevice, e->stream), "rows upload"));
+  PAL_TRY(e->check(hipMemcpyAsync(dp, pairs, size_t(2 * P) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream), "pairs upload"));
+  PAL_TRY(e->bootstrap_peaks_dev(static_cast<const double*>(df), R, L, static_cast<const int32_t*>(dp), P, num_bootstrap, mode, block_size,
+                                 seed, static_cast<double*>(dk)));
+  PAL_TRY(e->check(hipMemcpyAsync(peaks, dk, pbytes, hipMemcpyDeviceToHost, e->stream), "peaks download"));
+  return pal_synchronize(h);
+}
+
 static int single_pair(Engine* e, const double* sig1, int n1, const double* sig2, int n2, const pal_phat_params* prm,
                        int32_t* k_out, pal_pair_record* rec, double* corr) {
   if (!sig1 || !sig2) return e->fail(PAL_ERR_INVALID, "NULL signal");

@@ -13,7 +13,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, bootstrap
 from ._ffi import RECORD, PalError, PhatParams, f64, ptr
 
 
@@ -174,6 +174,34 @@ class Engine:
         """Asynchronous: rows[R][L], pairs[P][2] (int32) and table[P] stay in HBM (a rank's block of a large frame's pair list)."""
         self._check(self._lib.pal_gcc_phat_pairs_dev(self._h, C.c_void_p(d_rows), int(r), int(length), C.c_void_p(d_pairs), int(p),
                                                      C.byref(prm), C.c_void_p(d_table)))
+
+    # ---- bootstrap significance (utils.py:183-216; generator: bootstrap.py) -------------------
+    def bootstrap_peaks(self, rows, pairs, num_bootstrap=1000, mode="permutation", block_size=50, seed=0) -> np.ndarray:
+        """rows[R][L], pairs[P][2] -> peaks[P][num_bootstrap]: max PHAT(rows[i], shuffle s of rows[j]), shuffles keyed on
+        (seed, i, j, s) (bootstrap.shuffle_indices)."""
+        code = bootstrap.check_args(mode, block_size, num_bootstrap)
+        x = f64(rows)
+        if x.ndim != 2:
+            raise ValueError("rows must be [R][L]")
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        peaks = np.empty((pr.shape[0], int(num_bootstrap)))
+        self._check(self._lib.pal_bootstrap_peaks(self._h, x.ctypes.data, x.shape[0], x.shape[1], pr.ctypes.data, pr.shape[0],
+                                                  int(num_bootstrap), code, int(block_size), int(seed), peaks.ctypes.data))
+        return peaks
+
+    def bootstrap_shuffle_dev(self, d_row: int, length: int, i: int, j: int, mode, block_size: int, seed: int, s0: int, count: int,
+                              d_out: int) -> None:
+        """Asynchronous: shuffles s0 .. s0+count-1 of the row d_row[length] under the key (seed, i, j) -> d_out[count][length]."""
+        code = bootstrap.check_args(mode, block_size, count)
+        self._check(self._lib.pal_bootstrap_shuffle_dev(self._h, C.c_void_p(d_row), int(length), int(i), int(j), code, int(block_size),
+                                                        int(seed), int(s0), int(count), C.c_void_p(d_out)))
+
+    def bootstrap_peaks_dev(self, d_rows: int, r: int, length: int, d_pairs: int, p: int, num_bootstrap: int, mode, block_size: int,
+                            seed: int, d_peaks: int) -> None:
+        """Asynchronous: rows[R][L], pairs[P][2] (int32) and peaks[P][num_bootstrap] stay in HBM."""
+        code = bootstrap.check_args(mode, block_size, num_bootstrap)
+        self._check(self._lib.pal_bootstrap_peaks_dev(self._h, C.c_void_p(d_rows), int(r), int(length), C.c_void_p(d_pairs), int(p),
+                                                      int(num_bootstrap), code, int(block_size), int(seed), C.c_void_p(d_peaks)))
 
     def phat_correlation(self, sig1, sig2) -> np.ndarray:
         a, b = f64(sig1), f64(sig2)

@@ -17,7 +17,7 @@ from . import _ffi
 from .engine import default_engine, pair_list
 from .materials import material_properties  # module-level table, used regardless of config
 from .signal_processing import generate_signal, noise_reduction_rows
-from .utils import (bootstrap_significance, calculate_attenuation, compute_weights, distance, dynamic_bounds_extended,
+from .utils import (bootstrap_significance, bootstrap_thresholds, calculate_attenuation, compute_weights, distance, dynamic_bounds_extended,
                     equations, equations_jacobian, generate_image_sources_iterative, residuals, heuristic_initialization_adaptive, read_audio_files,
                     speed_of_sound, synchronize_signals_improved)
 
@@ -156,6 +156,8 @@ def localize_sound_source(config, calibration_data=None, audio_files=None, use_s
     clustering_eps = loc.get("clustering_eps", 0.001)
     clustering_min_samples = loc.get("clustering_min_samples", 2)
     max_expected_delay = loc.get("max_expected_delay", None)
+    bootstrap_rng = loc.get("bootstrap_rng", "numpy")        # "device": counter-based shuffles, all pairs in one call
+    bootstrap_seed = loc.get("bootstrap_seed", 0)
 
     calib_delays = None
     if calibration_data is not None:                                           # main.py:147-157
@@ -203,7 +205,10 @@ def localize_sound_source(config, calibration_data=None, audio_files=None, use_s
     td_diffs, mic_pairs = [], []
     corr_matrix = np.zeros((m, m))
     correlation_metrics: Dict[Any, Any] = {}
-    for row, (i, j) in zip(table, pairs):
+    thresholds = None
+    if analyze_correlation and bootstrap_rng == "device":
+        thresholds = bootstrap_thresholds(filtered, pairs, fs, alpha=0.05, seed=bootstrap_seed)
+    for p, (row, (i, j)) in enumerate(zip(table, pairs)):
         i, j = int(i), int(j)
         td = (np.int64(row["k_sel"]) - (n2 - 1)) / fs                          # time_lags[k] (utils.py:141-142)
         if calib_delays is not None:
@@ -212,7 +217,8 @@ def localize_sound_source(config, calibration_data=None, audio_files=None, use_s
         mic_pairs.append((i, j))
         if analyze_correlation:                                                # main.py:219-222, utils.py:261-271
             ratio = np.inf if row["cmin"] == 0 else row["cmax"] / abs(row["cmin"])
-            limit = bootstrap_significance(filtered[i], filtered[j], fs, alpha=0.05)
+            limit = thresholds[p] if thresholds is not None else \
+                bootstrap_significance(filtered[i], filtered[j], fs, alpha=0.05, rng=bootstrap_rng)
             snr = float(row["snr"])
             correlation_metrics[(i, j)] = {"peak_to_peak_ratio": ratio, "snr": snr,
                                            "significant": bool(row["cmax"] > limit) and snr > 2.0}

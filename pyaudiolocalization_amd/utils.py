@@ -13,6 +13,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
+from .bootstrap import check_args
 from .engine import default_engine, image_sources
 from .materials import material_properties  # noqa: F401  (re-exported like the reference does)
 
@@ -120,13 +121,23 @@ def compute_snr(corr: np.ndarray) -> float:
 
 # ---------------------------------------------------------------- significance (next row N1)
 def bootstrap_significance(sig1: np.ndarray, sig2: np.ndarray, fs: float, num_bootstrap: int = 1000, alpha: float = 0.05,
-                           bootstrap_mode: str = "permutation", block_size: int = 50, batch: int = 250) -> float:
-    """(1 - alpha) percentile of max(PHAT(sig1, shuffled sig2)) (utils.py:183-216).  The shuffles come from
-    the global NumPy RNG like the reference (so the result is statistically, not bitwise, comparable); the
-    PHAT correlations of a batch of shuffles run as ONE one-vs-many engine call."""
+                           bootstrap_mode: str = "permutation", block_size: int = 50, batch: int = 250, rng: str = "numpy",
+                           seed: int = 0) -> float:
+    """(1 - alpha) percentile of max(PHAT(sig1, shuffled sig2)) (utils.py:183-216).
+
+    rng="numpy" (default): the shuffles come from the global NumPy RNG like the reference (bitwise the reference's shuffles
+    under np.random.seed); the PHAT correlations of a batch of shuffles run as ONE one-vs-many engine call.
+    rng="device": counter-based shuffles drawn on the device (bootstrap.py), keyed on (seed, 0, 1, s) - statistically
+    equivalent to the reference's, not bitwise equal; equal lengths only."""
     if bootstrap_mode not in ("permutation", "block", "circular"):
         raise ValueError("unknown bootstrap_mode; use 'permutation', 'block' or 'circular'")
+    if rng not in ("numpy", "device"):
+        raise ValueError(f"unknown rng {rng!r}; use 'numpy' or 'device'")
     a, b = np.asarray(sig1, dtype=np.float64), np.asarray(sig2, dtype=np.float64)
+    if rng == "device":
+        if a.shape != b.shape:
+            raise ValueError("rng='device' needs sig1 and sig2 of equal length")
+        return float(bootstrap_thresholds(np.stack([a, b]), [[0, 1]], fs, num_bootstrap, alpha, bootstrap_mode, block_size, seed)[0])
     if a.shape != b.shape:            # unequal lengths: fall back to one engine call per shuffle
         batch = 1
     eng = default_engine()
@@ -149,6 +160,16 @@ def bootstrap_significance(sig1: np.ndarray, sig2: np.ndarray, fs: float, num_bo
         else:
             peaks.append(float(eng.get_time_delays_phat(a, rows[1], fs, want_corr=False)[1]["cmax"]))
     return np.percentile(peaks, 100 * (1 - alpha))
+
+
+def bootstrap_thresholds(rows, pairs, fs: float, num_bootstrap: int = 1000, alpha: float = 0.05,
+                         bootstrap_mode: str = "permutation", block_size: int = 50, seed: int = 0) -> np.ndarray:
+    """Bootstrap thresholds of every listed pair in one device call: rows[R][L], pairs[P][2] (row indices) -> [P], the
+    reference's np.percentile(peaks, 100 * (1 - alpha)) over the pair's num_bootstrap shuffles of rows[j] (utils.py:213-215).
+    The shuffles are counter-based and keyed on (seed, i, j, s) (bootstrap.py); the maximum does not depend on fs."""
+    check_args(bootstrap_mode, block_size, num_bootstrap)
+    peaks = default_engine().bootstrap_peaks(rows, pairs, num_bootstrap, bootstrap_mode, block_size, seed)
+    return np.percentile(peaks, 100 * (1 - alpha), axis=1)
 
 
 def perform_significance_test_bootstrap(sig1, sig2, fs, alpha: float = 0.05) -> Tuple[float, bool]:

@@ -178,8 +178,8 @@ struct CorrStorer {
 // correlation row is exactly zero (argmax 0, no peaks).  Here two pairs share one complex transform, whose rounding
 // leaves 1e-17 of the OTHER pair in that row: the rows of pairs with a silent microphone are therefore forced to zero.
 // The same pass looks for non-finite samples.  The reference confines a NaN to the pairs of its own microphone; here the
-// pair packed into the same complex transform would be poisoned as well, so a non-finite frame sets bit 2 of the
-// engine's status word and the call is reported as PAL_ERR_INVALID by pal_synchronize (never silently wrong rows).
+// pair packed into the same complex transform would be poisoned as well, so a non-finite frame sets kStInputNonFinite in the
+// engine's status word kStInput and the call is reported as PAL_ERR_INVALID by pal_synchronize (never silently wrong rows).
 __global__ __launch_bounds__(256) void k_row_nonzero(const double* __restrict__ frames, size_t frame_stride, int len, int* __restrict__ flags,
                                                      int* __restrict__ status) {
   const double* x = frames + size_t(blockIdx.x) * frame_stride;
@@ -193,12 +193,12 @@ __global__ __launch_bounds__(256) void k_row_nonzero(const double* __restrict__ 
   const int nonfinite = __syncthreads_or(bad ? 1 : 0);
   if (threadIdx.x == 0) {
     flags[blockIdx.x] = all;
-    if (nonfinite && status) atomicOr(status + 2, 1);
+    if (nonfinite && status) atomicOr(status + kStInput, kStInputNonFinite);
   }
 }
 
 // explicit pair list (row indices, two per pair) -> the packed table of the pair pipeline: two pairs per complex
-// transform, (c, d) = (-1, -1) when the count is odd.  A row index outside 0..R-1 sets bit 1 of status word 2 and the
+// transform, (c, d) = (-1, -1) when the count is odd.  A row index outside 0..R-1 sets kStInputBadRow in status word kStInput and the
 // pair is redirected to row 0 (no out-of-range read; pal_synchronize reports PAL_ERR_INVALID).
 __global__ __launch_bounds__(256) void k_pairs_to_quads(const int32_t* __restrict__ pairs, int64_t P, int R, int4* __restrict__ quads,
                                                         int* __restrict__ status) {
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void k_pairs_to_quads(const int32_t* __restric
     if (at < 2 * P && (v[q] < 0 || v[q] >= R)) { bad = true; v[q] = 0; }
   }
   quads[g] = make_int4(v[0], v[1], v[2], v[3]);
-  if (bad && status) atomicOr(status + 2, 2);
+  if (bad && status) atomicOr(status + kStInput, kStInputBadRow);
 }
 
 __global__ __launch_bounds__(256) void k_pair_zero(const int4* __restrict__ quads, const int* __restrict__ nonzero, int64_t ntr,
@@ -472,16 +472,15 @@ int Engine::forward_spectra(Plan& pl, const double* frames, size_t frame_stride,
   Engine* e = this;
   if (len > pl.lin) return fail(PAL_ERR_INVALID, "frame length %d exceeds plan input length %d", len, pl.lin);
   if (nonzero && rows > 0) {
-    void* stp = nullptr;
-    PAL_TRY(scratch(7, 64, &stp));
-    k_row_nonzero<<<dim3(rows), dim3(256), 0, stream>>>(frames, frame_stride, len, nonzero, static_cast<int*>(stp));
+    int* status = nullptr;
+    PAL_TRY(status_words(&status));
+    k_row_nonzero<<<dim3(rows), dim3(256), 0, stream>>>(frames, frame_stride, len, nonzero, status);
     PAL_HIP(hipGetLastError());
   }
   if (pfa_forward_applies(pl, len)) return pfa_forward_spectra(pl, frames, frame_stride, rows, len, spectra);
   const Conv& c = pl.fwd;
-  void* wsp = nullptr;
-  PAL_TRY(scratch(0, size_t(chunk) * c.M() * sizeof(cd), &wsp));
-  cd* W = static_cast<cd*>(wsp);
+  cd* W = nullptr;
+  PAL_TRY(scratch(kWsWork, size_t(chunk) * c.M() * sizeof(cd), &W));
   for (int r0 = 0; r0 < rows; r0 += chunk) {
     const int G = rows - r0 < chunk ? rows - r0 : chunk;
     FrameLoader ld{frames + size_t(r0) * frame_stride, frame_stride, len, pl.w};
@@ -508,65 +507,53 @@ int Engine::pairs_dev(const double* d_rows, int R, int L, const int32_t* d_pairs
   if (L > (1 << 20)) return fail(PAL_ERR_UNSUPPORTED, "frame length %d exceeds 2^20", L);
   Plan* pl = nullptr;
   PAL_TRY(get_plan(2 * L - 1, L, 2 * L - 1, &pl));
-  void *sp = nullptr, *dq = nullptr, *stp = nullptr;
-  PAL_TRY(scratch(2, size_t(R) * pl->spec_stride() * sizeof(cd) + size_t(R) * sizeof(int), &sp));
-  int* nonzero = reinterpret_cast<int*>(static_cast<cd*>(sp) + size_t(R) * pl->spec_stride());
+  cd* sp = nullptr;
+  int4* dq = nullptr;
+  int* status = nullptr;
+  PAL_TRY(scratch(kWsSpectra, size_t(R) * pl->spec_stride() * sizeof(cd) + size_t(R) * sizeof(int), &sp));
+  int* nonzero = reinterpret_cast<int*>(sp + size_t(R) * pl->spec_stride());
   const int64_t ntr = (P + 1) / 2;
-  PAL_TRY(scratch(3, size_t(ntr) * sizeof(int4), &dq));
-  PAL_TRY(scratch(7, 64, &stp));
-  k_pairs_to_quads<<<dim3(unsigned((ntr + 255) / 256)), dim3(256), 0, stream>>>(d_pairs, P, R, static_cast<int4*>(dq), static_cast<int*>(stp));
+  PAL_TRY(scratch(kWsQuads, size_t(ntr) * sizeof(int4), &dq));
+  PAL_TRY(status_words(&status));
+  k_pairs_to_quads<<<dim3(unsigned((ntr + 255) / 256)), dim3(256), 0, stream>>>(d_pairs, P, R, dq, status);
   PAL_HIP(hipGetLastError());
-  PAL_TRY(forward_spectra(*pl, d_rows, size_t(L), R, L, static_cast<cd*>(sp), nonzero));
-  return pair_correlations(*pl, static_cast<const cd*>(sp), R, static_cast<const int4*>(dq), P, L, prm, d_table, nullptr, nullptr, nonzero);
+  PAL_TRY(forward_spectra(*pl, d_rows, size_t(L), R, L, sp, nonzero));
+  return pair_correlations(*pl, sp, R, dq, P, L, prm, d_table, nullptr, nullptr, nonzero);
 }
 
 int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4* quads, int64_t npairs, int n2,
                               const pal_phat_params& prm, pal_pair_record* table, int32_t* ksel_multi,
-                              double* corr_out, const int* nonzero) {
-  Engine* e = this;
+                              double* corr_out, const int* nonzero, bool stored_only) {
   const Conv& c = pl.inv;
   const int n = pl.n;
   const bool pfa = pl.pfa.on();
   const int chunk = pair_group(n);   // (shadows the engine-wide group size: larger groups amortise launch tails and the peak kernels' fixed costs)
-  const cd* permuted = spectra;   // forward_spectra wrote the (k mod N1, k mod N2) layout when the plan has the split
-  (void)nspec;
   // Launch groups rotate over three HIP streams, each with its own workspace and correlation buffer: the
   // memory-bound head and tail of one group's kernels overlap the LDS/VALU-bound middle of the others', and the
   // peak kernels of group g run beside the FFT passes of group g+1.  Same-slot reuse is ordered by the stream.
   const int nslot = !one_stream && table != nullptr ? 3 : 1;
   const size_t wpoints = size_t(chunk) * (pfa ? size_t(n) : c.M());
-  void* wsp = nullptr;
-  PAL_TRY(scratch(0, size_t(nslot) * wpoints * sizeof(cd), &wsp));
-  cd* W = static_cast<cd*>(wsp);
+  cd* W = nullptr;
+  PAL_TRY(scratch(kWsWork, size_t(nslot) * wpoints * sizeof(cd), &W));
   const size_t stride = corr_out ? size_t(n) : (size_t(n) + 1) & ~size_t(1);
   const size_t buf_doubles = size_t(2 * chunk) * stride;
-  void* p = nullptr;
-  PAL_TRY(scratch(1, size_t(nslot) * buf_doubles * sizeof(double), &p));
-  double* cbuf = static_cast<double*>(p);
+  double* cbuf = nullptr;
+  PAL_TRY(scratch(kWsCorr, size_t(nslot) * buf_doubles * sizeof(double), &cbuf));
   const int64_t ntr = (npairs + 1) / 2;
   int* zero_rows = nullptr;
   if (nonzero && ntr > 0) {
-    void* zp = nullptr;
-    PAL_TRY(scratch(14, size_t(2 * ntr) * sizeof(int), &zp));
-    zero_rows = static_cast<int*>(zp);
+    PAL_TRY(scratch(kWsZeroRows, size_t(2 * ntr) * sizeof(int), &zero_rows));
     k_pair_zero<<<dim3(unsigned((ntr + 255) / 256)), dim3(256), 0, stream>>>(quads, nonzero, ntr, zero_rows);
     PAL_HIP(hipGetLastError());
   }
-  // the finishing column pass (pfa_cols_fin.h) writes one flag per pair: 1 = resolved at the end of this call from stored rows
-  const bool fin = table && pfa && !corr_out && !ksel_multi && pfa_can_finish(pl, prm);
-  // stored rows + per-wavefront statistics (pfa_fin_lean.h with FinArgs.corr): the caller wants corr, or the plan has no finishing form
-  const bool lean = !fin && pfa && table && !ksel_multi && pfa_can_lean_store(pl, prm);
-  // rows of any other route: their statistics in one launch over the stored rows (k_rows_lean)
-  // (calls of at least 200 000 pairs: the end-of-call count and the flagged rows' second pass - 1.8 % of the rows at C5's lag window -
-  //  cost the 30 000 - 80 000-pair calls of the stream chain more than the launch saves, and stall its host: 480 - 497 against 527 - 535 frames/s)
-  const bool rlean = !fin && !lean && table && !ksel_multi && npairs >= rows_lean_min && rows_can_lean(pl, prm) &&
-                     !(pfa && pfa_can_fuse(pl));
+  // who transforms a launch group and who computes its rows' statistics: one decision per call (pair_route.h)
+  const Pfa& f = pl.pfa;
+  const PairRoute route = pair_route(RouteIn{n, pl.nout, pfa, f.n1, f.n2, f.nch, f.lm, f.r89 != nullptr, table != nullptr, corr_out != nullptr,
+                                             ksel_multi != nullptr, npairs, stored_only, prm.num_peaks, prm.threshold_method, prm.threshold_multiplier,
+                                             fin_cols, fuse_peaks, lean_store, rows_lean, rows_lean_min});
+  // the finishing passes and k_rows_lean write one flag per pair: 1 = resolved at the end of this call from stored rows
   int* need = nullptr;
-  if (fin || lean || rlean) {
-    void* np = nullptr;
-    PAL_TRY(scratch(19, (size_t(2 * npairs) + 64) * sizeof(int), &np));     // [flags | list | count]
-    need = static_cast<int*>(np);
-  }
+  if (route.flags_pairs()) PAL_TRY(scratch(kWsFlags, (size_t(2 * npairs) + 64) * sizeof(int), &need));     // [flags | list | count]
   if (nslot == 3) {   // the other streams start after everything already queued on `stream` (spectra, pair table)
     PAL_HIP(hipEventRecord(ev_fork, stream));
     PAL_HIP(hipStreamWaitEvent(stream2, ev_fork, 0));
@@ -578,39 +565,38 @@ int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4
     const int64_t p0 = 2 * t0;
     const int rows = int(npairs - p0 < 2 * G ? npairs - p0 : 2 * G);
     const int slot = int(group % nslot);
-    hipStream_t on = slot == 0 ? stream : (slot == 1 ? stream2 : stream3);
+    const hipStream_t on = stream_of(slot);
     prof_gate = prof_every <= 1 || (prof_tick++ % prof_every) == 0;
     cd* Wg = W + size_t(slot) * wpoints;
     // odd tail with a caller buffer: the imaginary half of the last transform has no destination row there
     const bool via_scratch = !corr_out || rows < 2 * G;
     double* crow = via_scratch ? cbuf + size_t(slot) * buf_doubles : corr_out + size_t(p0) * stride;
-    const bool fused = pfa && table && pfa_can_fuse(pl);
-    if (lean) {
-      PAL_TRY(pfa_pair_group_fin(pl, permuted, quads + t0, G, rows, Wg, zero_rows ? zero_rows + p0 : nullptr, prm, n2, table + p0, need + p0,
-                                 slot, on, crow, stride));
-    } else if (fin) {
-      // nobody reads the correlation rows: the column pass finishes them without storing them (pfa_cols_fin.h)
-      PAL_TRY(pfa_pair_group_fin(pl, permuted, quads + t0, G, rows, Wg, zero_rows ? zero_rows + p0 : nullptr, prm, n2, table + p0, need + p0,
-                                 slot, on));
-    } else if (fused) {
-      PAL_TRY(pfa_pair_group_fused(pl, permuted, quads + t0, G, rows, Wg, crow, stride, zero_rows ? zero_rows + p0 : nullptr, prm, n2, table + p0,
-                                   ksel_multi ? ksel_multi + p0 * PAL_MAX_PEAKS : nullptr, on));
-    } else if (pfa) {
-      PAL_TRY(pfa_pair_group(pl, permuted, quads + t0, G, Wg, crow, stride, zero_rows ? zero_rows + p0 : nullptr, on));
-    } else {
-      PairLoader ld{spectra, quads + t0, n, pl.H, pl.w};
-      PAL_TRY(launch_cols_fwd(e, c, G, ld, Wg, on));
-      PAL_TRY(launch_rows(e, c, G, Wg, true, 1.0, on));
-      CorrStorer st{crow, stride, n, pl.w, zero_rows ? zero_rows + p0 : nullptr};
-      PAL_TRY(launch_cols_inv(e, c, G, Wg, st, on));
+    const int* zrows = zero_rows ? zero_rows + p0 : nullptr;
+    int32_t* ksel = ksel_multi ? ksel_multi + p0 * PAL_MAX_PEAKS : nullptr;
+    switch (route.transform) {   // (forward_spectra wrote the (k mod N1, k mod N2) layout when the plan has the split)
+      case RouteTransform::kFinish:      // nobody reads the correlation rows: the column pass finishes them without storing them (pfa_cols_fin.h)
+        PAL_TRY(pfa_pair_group_fin(pl, spectra, quads + t0, G, rows, Wg, zrows, prm, n2, table + p0, need + p0, slot)); break;
+      case RouteTransform::kLeanStore:   // stored rows + per-wavefront statistics (pfa_fin_lean.h with FinArgs.corr)
+        PAL_TRY(pfa_pair_group_fin(pl, spectra, quads + t0, G, rows, Wg, zrows, prm, n2, table + p0, need + p0, slot, crow, stride)); break;
+      case RouteTransform::kFused:
+        PAL_TRY(pfa_pair_group_fused(pl, spectra, quads + t0, G, rows, Wg, crow, stride, zrows, prm, n2, table + p0, ksel, slot)); break;
+      case RouteTransform::kPfa:
+        PAL_TRY(pfa_pair_group(pl, spectra, quads + t0, G, Wg, crow, stride, zrows, on)); break;
+      case RouteTransform::kFourStep: {
+        PairLoader ld{spectra, quads + t0, n, pl.H, pl.w};
+        PAL_TRY(launch_cols_fwd(this, c, G, ld, Wg, on));
+        PAL_TRY(launch_rows(this, c, G, Wg, true, 1.0, on));
+        CorrStorer st{crow, stride, n, pl.w, zrows};
+        PAL_TRY(launch_cols_inv(this, c, G, Wg, st, on));
+        break;
+      }
     }
     if (corr_out && via_scratch)
       PAL_HIP(hipMemcpyAsync(corr_out + size_t(p0) * stride, crow, size_t(rows) * stride * sizeof(double),
                              hipMemcpyDeviceToDevice, on));
-    if (rlean)
-      PAL_TRY(rows_lean_group(pl, crow, stride, G, rows, prm, n2, table + p0, need + p0, slot, on));
-    else if (table && !fused && !fin && !lean)
-      PAL_TRY(peaks(crow, stride, rows, n, n2, prm, table + p0, ksel_multi ? ksel_multi + p0 * PAL_MAX_PEAKS : nullptr, on));
+    // rows of the plain routes: their statistics in one launch over the stored rows, or in three
+    if (route.stats == RouteStats::kRowsLean) PAL_TRY(rows_lean_group(pl, crow, stride, G, rows, prm, n2, table + p0, need + p0, slot));
+    else if (route.stats == RouteStats::kThreeLaunches) PAL_TRY(peaks(crow, stride, rows, n, n2, prm, table + p0, ksel, slot));
     return PAL_OK;
   };
   int64_t group = 0;
@@ -635,7 +621,7 @@ int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4
     PAL_HIP(hipEventRecord(ev_join3, stream3));
     PAL_HIP(hipStreamWaitEvent(stream, ev_join3, 0));
   }
-  if (fin || lean || rlean) {
+  if (route.flags_pairs()) {
     // The pairs the finishing blocks flagged (a threshold comparison inside the median's interval, a tie, a window peak next to
     // the window's edge, ...) go through the stored-row path now, packed in pair order.  The count comes to the host: this
     // is the one synchronisation of the call (its launch groups above never waited for the host).
@@ -647,19 +633,14 @@ int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4
     PAL_HIP(hipMemcpyAsync(&count, dcount, sizeof count, hipMemcpyDeviceToHost, stream));
     PAL_HIP(hipStreamSynchronize(stream));
     if (count > 0) {                                           // `count` transforms hold a flagged pair
-      void *qp = nullptr, *tp = nullptr;
-      PAL_TRY(scratch(20, size_t(count) * sizeof(int4), &qp));
-      PAL_TRY(scratch(21, size_t(2 * count) * sizeof(pal_pair_record), &tp));
-      k_flag_quads<<<dim3(unsigned((count + 255) / 256)), dim3(256), 0, stream>>>(quads, list, count, static_cast<int4*>(qp));
+      int4* qp = nullptr;
+      pal_pair_record* tp = nullptr;
+      PAL_TRY(scratch(kWsFlagQuads, size_t(count) * sizeof(int4), &qp));
+      PAL_TRY(scratch(kWsFlagTable, size_t(2 * count) * sizeof(pal_pair_record), &tp));
+      k_flag_quads<<<dim3(unsigned((count + 255) / 256)), dim3(256), 0, stream>>>(quads, list, count, qp);
       PAL_HIP(hipGetLastError());
-      const bool keep = fin_cols;
-      fin_cols = false;
-      const int rc = pair_correlations(pl, spectra, nspec, static_cast<const int4*>(qp), int64_t(2) * count, n2, prm, static_cast<pal_pair_record*>(tp),
-                                       nullptr, nullptr, nonzero);
-      fin_cols = keep;
-      PAL_TRY(rc);
-      k_flag_scatter<<<dim3(unsigned((2 * count + 255) / 256)), dim3(256), 0, stream>>>(static_cast<const pal_pair_record*>(tp), list, count, need,
-                                                                                      npairs, table);
+      PAL_TRY(pair_correlations(pl, spectra, nspec, qp, int64_t(2) * count, n2, prm, tp, nullptr, nullptr, nonzero, true));   // stored rows only: nothing that flags again
+      k_flag_scatter<<<dim3(unsigned((2 * count + 255) / 256)), dim3(256), 0, stream>>>(tp, list, count, need, npairs, table);
       PAL_HIP(hipGetLastError());
     }
   }

@@ -23,7 +23,7 @@ struct BootShuffle {
   uint64_t seed;
   double* out;               // [C][L]
   int32_t* round_pairs;      // [C][2] = (i, R + c) for the pair pipeline, or nullptr
-  int* status;               // bit 1 of word 2: a row index outside 0..R-1 (reported by pal_synchronize)
+  int* status;               // kStInputBadRow: a row index outside 0..R-1 (reported by pal_synchronize)
 };
 
 constexpr int kBootPerThread = 4;
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void k_bootstrap_shuffle(BootShuffle a) {
     i = a.pairs[2 * p];
     j = a.pairs[2 * p + 1];
     const bool bad = i < 0 || i >= a.R || j < 0 || j >= a.R;
-    if (bad && blockIdx.y == 0 && threadIdx.x == 0 && a.status) atomicOr(a.status + 2, 2);
+    if (bad && blockIdx.y == 0 && threadIdx.x == 0 && a.status) atomicOr(a.status + kStInput, kStInputBadRow);
     if (i < 0 || i >= a.R) i = 0;
     if (j < 0 || j >= a.R) j = 0;
     src = a.rows + size_t(j) * size_t(a.L);
@@ -115,23 +115,22 @@ int Engine::bootstrap_peaks_dev(const double* d_rows, int R, int L, const int32_
   if (int64_t(R) + Cmax > INT32_MAX / 2) return fail(PAL_ERR_UNSUPPORTED, "too many rows");
   const size_t ss = pl->spec_stride();
   const int rows = R + Cmax;
-  void *sp = nullptr, *xp = nullptr, *pp = nullptr, *rp = nullptr, *stp = nullptr;
+  cd* spectra = nullptr;
+  double* shuffled = nullptr;
+  char* pp = nullptr;
+  int* status = nullptr;
   // spectra of the R rows, then of the round's shuffled rows; one non-zero flag per row behind them
-  PAL_TRY(scratch(2, size_t(rows) * ss * sizeof(cd) + size_t(rows) * sizeof(int), &sp));
-  PAL_TRY(scratch(10, size_t(Cmax) * size_t(L) * sizeof(double), &xp));
+  PAL_TRY(scratch(kWsSpectra, size_t(rows) * ss * sizeof(cd) + size_t(rows) * sizeof(int), &spectra));
+  PAL_TRY(scratch(kWsBootRows, size_t(Cmax) * size_t(L) * sizeof(double), &shuffled));
   // the round's tables: [pair list (i, R + c) | packed transforms | records]
   const size_t quad_off = (size_t(2 * Cmax) * sizeof(int32_t) + 15) & ~size_t(15);
   const size_t rec_off = quad_off + size_t((Cmax + 1) / 2) * sizeof(int4);
-  PAL_TRY(scratch(11, rec_off + size_t(Cmax) * sizeof(pal_pair_record), &pp));
-  rp = static_cast<char*>(pp) + rec_off;
-  PAL_TRY(scratch(7, 64, &stp));
-  cd* spectra = static_cast<cd*>(sp);
+  PAL_TRY(scratch(kWsBootRound, rec_off + size_t(Cmax) * sizeof(pal_pair_record), &pp));
+  PAL_TRY(status_words(&status));
   int* nonzero = reinterpret_cast<int*>(spectra + size_t(rows) * ss);
-  double* shuffled = static_cast<double*>(xp);
-  int32_t* round_pairs = static_cast<int32_t*>(pp);
-  int4* quads = reinterpret_cast<int4*>(static_cast<char*>(pp) + quad_off);
-  pal_pair_record* rec = static_cast<pal_pair_record*>(rp);
-  int* status = static_cast<int*>(stp);
+  int32_t* round_pairs = reinterpret_cast<int32_t*>(pp);
+  int4* quads = reinterpret_cast<int4*>(pp + quad_off);
+  pal_pair_record* rec = reinterpret_cast<pal_pair_record*>(pp + rec_off);
   // default peak selection (median, no lag window); only cmax = np.max(corr) is read
   pal_phat_params prm{};
   prm.fs = 1000.0;

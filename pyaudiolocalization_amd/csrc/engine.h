@@ -13,12 +13,13 @@
 #include "../../include/pal_hip.h"
 #include "fin_scratch.h"
 #include "fft_core.h"
+#include "pair_route.h"
+#include "peak_types.h"
 
 namespace pal {
 
 // One circular convolution of length M = M1 x M2 (four-step, both factors in LDS).
 // M2 = 2^l2; M1 = 2^l1, or 3 * 2^l1 (r3) when the 3 * 2^k length is the smaller fit.
-struct PeakArgs;    // peak_types.h
 struct FinArgs;     // pfa_cols_fin.h
 
 struct Conv {
@@ -79,12 +80,33 @@ struct ProfileSlot {
   int64_t launches = 0;
 };
 
+// The engine's growable device scratch blocks (Engine::scratch), by number.  (caller): held by a caller across a call into the pair
+// pipeline (pair_correlations and what it launches), which therefore never takes them; it takes the others.
+enum Ws : int {
+  kWsWork = 0,         // transform workspace of a launch group, one per stream slot (also the forward spectra's and sim.hip's)
+  kWsCorr = 1,         // correlation rows of a launch group, one per stream slot (sim.hip: filter / correlation rows)
+  kWsSpectra = 2,      // (caller) spectra + non-zero flags of a call's rows: all_pairs_dev, pairs_dev, the bootstrap
+  kWsQuads = 3,        // (caller) packed transforms of an explicit pair list (pairs_dev); small tables of sim.hip
+  kWsStageIn = 4, kWsStageTable = 5, kWsStageOut = 6, kWsStagePairs = 15,   // (caller) API staging: uploaded rows, records / per-row results, rows out, a pair list
+  kWsStatus = 7,       // the status words (peak_types.h StatusWord), see status_words()
+  kWsPeaks0 = 8, kWsPeaks1 = 9, kWsPeaks2 = 12,         // peak selection (peaks.hip) per stream slot, see peak_scratch_slot
+  kWsBootRows = 10, kWsBootRound = 11, kWsBootPeaks = 13,   // (caller) the bootstrap's shuffled rows, round tables (pair list, transforms, records), host-call peaks
+  kWsZeroRows = 14,    // per row of a call: a microphone of the pair is silent (k_pair_zero)
+  kWsFin0 = 16, kWsFin1 = 17, kWsFin2 = 18,             // the finishing column pass (pfa_cols_fin.h, fin_scratch.h) per stream slot, see fin_scratch_slot
+  kWsFlags = 19, kWsFlagQuads = 20, kWsFlagTable = 21,  // its flagged pairs: [flags | list | count], their packed transforms, their repaired records
+  kWsBlockTable = 23,  // (caller) records in blocked pair order (all_pairs_dev, large arrays); 22 is free
+  kWsCount = 24
+};
+constexpr Ws peak_scratch_slot(int slot) { return slot == 0 ? kWsPeaks0 : (slot == 1 ? kWsPeaks1 : kWsPeaks2); }
+constexpr Ws fin_scratch_slot(int slot) { return Ws(kWsFin0 + slot); }
+
 struct Engine {
   int device = 0;
   int cu_count = 256;              // compute units of the device (persistent kernels size their grids with it)
   hipStream_t stream = nullptr;    // FFT passes, copies, everything a caller can order against
   hipStream_t stream2 = nullptr;   // second and third launch-group slots (pair_correlations; PAL_OVERLAP=0: `stream` only)
   hipStream_t stream3 = nullptr;
+  hipStream_t stream_of(int slot) const { return slot == 0 ? stream : (slot == 1 ? stream2 : stream3); }   // launch-group slot -> its stream
   hipEvent_t ev_fork = nullptr, ev_join2 = nullptr, ev_join3 = nullptr;   // side slots start behind `stream`; `stream` waits for them at the end
   hipEvent_t ev_fin = nullptr;     // end of the latest finishing column pass (pfa_cols_fin.h): they run one at a time, see fin_serialize
   int fin_serialize(hipStream_t on);   // before such a launch: wait for the previous one; fin_done(on) behind it
@@ -124,9 +146,8 @@ struct Engine {
   cd* stage_tw[16] = {};                        // stage-major twiddles per log2 N (<= 14: the big row tiles of pfa_big.h)
   cd* stage_twc[16] = {};                       // the same with a compact last stage (fft_core.h stage_twc_size)
   // growable device scratch
-  void* ws[24] = {};              // (16..18: per-stream scratch of the finishing column pass, pfa_cols_fin.h; 19..21: its flagged pairs;
-                                  //  8, 9, 12: per-stream peak selection, peaks.hip; 10, 11, 13: the bootstrap's shuffled rows, round tables, host-call peaks)
-  size_t ws_bytes[24] = {};
+  void* ws[kWsCount] = {};
+  size_t ws_bytes[kWsCount] = {};
   // profiling
   bool profiling = false;
   int prof_every = 1;              // pair pipeline: events around every prof_every-th launch group only
@@ -151,7 +172,14 @@ struct Engine {
 
   int fail(int code, const char* fmt, ...);
   int check(hipError_t e, const char* what);
-  int scratch(int idx, size_t bytes, void** out);
+  int scratch(Ws idx, size_t bytes, void** out);
+  template <class T> int scratch(Ws idx, size_t bytes, T** out) {   // the same block as a T*
+    void* p = nullptr;
+    const int rc = scratch(idx, bytes, &p);
+    *out = static_cast<T*>(p);
+    return rc;
+  }
+  int status_words(int** out) { return scratch(kWsStatus, kStatusWords * sizeof(int), out); }   // peak_types.h StatusWord; zeroed when first taken
   const cd* stage_table(int ln);
   const cd* stage_table_compact(int ln);
   int build_pfa(Plan& pl);                  // pfa.hip: choose the split and make the tables (leaves pl.pfa off if none fits)
@@ -176,7 +204,7 @@ struct Engine {
   int forward_spectra(Plan& pl, const double* frames, size_t frame_stride, int rows, int len, cd* spectra, int* nonzero = nullptr);
   int pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4* quads, int64_t npairs, int n2,
                         const pal_phat_params& prm, pal_pair_record* table, int32_t* ksel_multi, double* corr_out,
-                        const int* nonzero = nullptr);
+                        const int* nonzero = nullptr, bool stored_only = false);   // stored_only: the repair pass of flagged pairs (pair_route.h)
   int pairs_dev(const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P, const pal_phat_params& prm,
                 pal_pair_record* d_table);
   // bootstrap.hip: counter-based shuffles (pal_bootstrap_shuffle_dev) and the shuffled pairs through the pair pipeline, round by round
@@ -186,28 +214,22 @@ struct Engine {
   int bootstrap_peaks_dev(const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P, int32_t S, int32_t mode, int32_t block_size,
                           uint64_t seed, double* d_peaks);
   int peaks(const double* corr, size_t stride, int rows, int n, int n2, const pal_phat_params& prm,
-            pal_pair_record* table, int32_t* ksel_multi, hipStream_t on);
+            pal_pair_record* table, int32_t* ksel_multi, int slot);
   // the same in pieces, for the column pass that produces the streaming statistics itself (pfa_cols_stats.h):
   // arguments + scratch (segments = `blocks` column blocks of a grid with rows of grid_n2, each with its own pivots),
   // [the caller's fused column launch], the finish launch
-  int peaks_setup(const double* corr, size_t stride, int rows, int n, int n2, const pal_phat_params& prm, int blocks, int grid_n2,
-                  hipStream_t on, PeakArgs& a);
-  int peaks_finish(PeakArgs& a, int rows, pal_pair_record* table, int32_t* ksel_multi, hipStream_t on);
+  int peaks_setup(const double* corr, size_t stride, int rows, int n, int n2, const pal_phat_params& prm, int blocks, int grid_n2, int slot, PeakArgs& a);
+  int peaks_finish(PeakArgs& a, int rows, pal_pair_record* table, int32_t* ksel_multi, int slot);
   int pfa_rows(const Plan& pl, const cd* permuted, const int4* quads, int G, cd* Y, hipStream_t on);
-  bool pfa_can_fuse(const Plan& pl) const;
   int fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, const pal_phat_params& prm, int n2, pal_pair_record* table,
-                int* need, int slot, hipStream_t on, PeakArgs& a, struct FinArgs& fa, unsigned& nwg, int G);
-  bool pfa_can_finish(const Plan& pl, const pal_phat_params& prm) const;   // pfa_cols_fin.h applies (one peak per row, N1 of 2..4 chunks)
-  bool rows_can_lean(const Plan& pl, const pal_phat_params& prm) const;        // k_rows_lean instead of pivots + stream + finish
+                int* need, int slot, PeakArgs& a, struct FinArgs& fa, unsigned& nwg, int G);
   int rows_lean_group(const Plan& pl, const double* corr, size_t stride, int G, int rows, const pal_phat_params& prm, int n2,
-                      pal_pair_record* table, int* need, int slot, hipStream_t on);
-  bool pfa_can_lean_store(const Plan& pl, const pal_phat_params& prm) const;   // the per-wavefront statistics beside STORED rows (pfa_fin_lean.h)
+                      pal_pair_record* table, int* need, int slot);
   int pfa_pair_group_fin(const Plan& pl, const cd* permuted, const int4* quads, int G, int rows, cd* Y, const int* zero_rows,
-                         const pal_phat_params& prm, int n2, pal_pair_record* table, int* need, int slot, hipStream_t on,
+                         const pal_phat_params& prm, int n2, pal_pair_record* table, int* need, int slot,
                          double* corr = nullptr, size_t stride = 0);
   int pfa_pair_group_fused(const Plan& pl, const cd* permuted, const int4* quads, int G, int rows, cd* Y, double* corr, size_t stride,
-                           const int* zero_rows, const pal_phat_params& prm, int n2, pal_pair_record* table, int32_t* ksel_multi,
-                           hipStream_t on);
+                           const int* zero_rows, const pal_phat_params& prm, int n2, pal_pair_record* table, int32_t* ksel_multi, int slot);
   bool pfa_forward_applies(const Plan& pl, int len) const;
   int pfa_forward_spectra(Plan& pl, const double* frames, size_t frame_stride, int rows, int len, cd* spectra);
   bool pfa_forward = true;    // PAL_PFA_FWD=0: forward spectra on the four-step route even where the prime-factor cut applies

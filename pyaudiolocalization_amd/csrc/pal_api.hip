@@ -27,7 +27,7 @@ int Engine::check(hipError_t e, const char* what) {
   return fail(code, "%s: %s", what, hipGetErrorString(e));
 }
 
-int Engine::scratch(int idx, size_t bytes, void** out) {
+int Engine::scratch(Ws idx, size_t bytes, void** out) {
   if (ws_bytes[idx] < bytes) {
     if (ws[idx]) {                       // either stream may still be using the old block
       PAL_HIP(hipStreamSynchronize(stream));
@@ -94,46 +94,38 @@ void Engine::prof_flush() {
   ev_used = 0;
 }
 
-// ---- status word written by k_peaks on an internal overflow ----
+// ---- the status words (peak_types.h StatusWord): one read, then what was reported is cleared ----
 static int check_status(Engine* e) {
-  if (!e->ws[7]) return PAL_OK;
-  int st = 0;
-  int rc = e->check(hipMemcpy(&st, e->ws[7], sizeof st, hipMemcpyDeviceToHost), "status read");
-  if (rc != PAL_OK) return rc;
+  int* dev = static_cast<int*>(e->ws[kWsStatus]);
+  if (!dev) return PAL_OK;
+  int st[kStatusWords] = {};
+  PAL_TRY(e->check(hipMemcpy(st, dev, sizeof st, hipMemcpyDeviceToHost), "status read"));
   if (getenv("PAL_DEBUG_FALLBACK")) {   // diagnostics: rows whose median needed the radix select since the last report
-    int slow = 0, exact = 0;
-    if (hipMemcpy(&slow, static_cast<int*>(e->ws[7]) + 1, sizeof slow, hipMemcpyDeviceToHost) == hipSuccess && slow) {
-      fprintf(stderr, "[pal] %d row(s) took the radix-select fallback\n", slow);
-      hipMemset(static_cast<int*>(e->ws[7]) + 1, 0, sizeof slow);
+    if (st[kStRadixFallback]) {
+      fprintf(stderr, "[pal] %d row(s) took the radix-select fallback\n", st[kStRadixFallback]);
+      hipMemset(dev + kStRadixFallback, 0, sizeof(int));
     }
-    if (hipMemcpy(&exact, static_cast<int*>(e->ws[7]) + 3, sizeof exact, hipMemcpyDeviceToHost) == hipSuccess && exact) {
-      fprintf(stderr, "[pal] %d row(s) needed the exact median (a threshold comparison inside the histogram interval)\n", exact);
-      hipMemset(static_cast<int*>(e->ws[7]) + 3, 0, sizeof exact);
+    if (st[kStExactMedian]) {
+      fprintf(stderr, "[pal] %d row(s) needed the exact median (a threshold comparison inside the histogram interval)\n", st[kStExactMedian]);
+      hipMemset(dev + kStExactMedian, 0, sizeof(int));
     }
-    int flagged = 0;
-    if (hipMemcpy(&flagged, static_cast<int*>(e->ws[7]) + 4, sizeof flagged, hipMemcpyDeviceToHost) == hipSuccess && flagged) {
-      int why[8] = {};
-      (void)hipMemcpy(why, static_cast<int*>(e->ws[7]) + 5, sizeof why, hipMemcpyDeviceToHost);
-      int gaveup = 0;
-      (void)hipMemcpy(&gaveup, static_cast<int*>(e->ws[7]) + 13, sizeof gaveup, hipMemcpyDeviceToHost);
+    if (st[kStFlagged]) {
+      const int* why = st + kStWhy;
       fprintf(stderr, "[pal] %d row(s) of the finishing column pass went through the stored-row path (no maximum / abandoned %d, tie %d, tie in window %d, "
                       "SNR window energy %d, histogram windows %d, threshold interval %d, window interval %d, window edge %d; waits given up %d)\n",
-              flagged, why[0], why[1], why[2], why[3], why[4], why[5], why[6], why[7], gaveup);
-      hipMemset(static_cast<int*>(e->ws[7]) + 4, 0, sizeof flagged + sizeof why);
-      hipMemset(static_cast<int*>(e->ws[7]) + 13, 0, sizeof gaveup);
+              st[kStFlagged], why[0], why[1], why[2], why[3], why[4], why[5], why[6], why[7], st[kStGaveUp]);
+      hipMemset(dev + kStFlagged, 0, (1 + kStWhyCount) * sizeof(int));
+      hipMemset(dev + kStGaveUp, 0, sizeof(int));
     }
   }
-  int in = 0;                                // word 2: input problems found by device-side checks
-  rc = e->check(hipMemcpy(&in, static_cast<int*>(e->ws[7]) + 2, sizeof in, hipMemcpyDeviceToHost), "status read");
-  if (rc != PAL_OK) return rc;
-  if (in) {
-    hipMemset(static_cast<int*>(e->ws[7]) + 2, 0, sizeof in);
-    if (in & 2) return e->fail(PAL_ERR_INVALID, "pair list references a row outside the frame batch");
+  if (st[kStInput]) {                        // input problems found by device-side checks
+    hipMemset(dev + kStInput, 0, sizeof(int));
+    if (st[kStInput] & kStInputBadRow) return e->fail(PAL_ERR_INVALID, "pair list references a row outside the frame batch");
     return e->fail(PAL_ERR_INVALID, "non-finite sample (NaN or infinity) in a frame: the pair packed with that microphone's "
                                     "pairs would be affected too, the table of this call is not valid");
   }
-  if (st) {
-    hipMemset(e->ws[7], 0, sizeof st);
+  if (st[kStOverflow]) {
+    hipMemset(dev + kStOverflow, 0, sizeof(int));
     return e->fail(PAL_ERR_INTERNAL, "peak selection: suppression chain exceeded the on-chip memo/stack (rows fell back to argmax)");
   }
   return PAL_OK;
@@ -199,7 +191,7 @@ static int all_pairs_dev(Engine* e, const double* d_frames, int B, int M, int L,
   PAL_TRY(e->get_plan(2 * L - 1, L, 2 * L - 1, &pl));
   const int rows = B * M;
   void* sp = nullptr;
-  PAL_TRY(e->scratch(2, size_t(rows) * pl->spec_stride() * sizeof(cd) + size_t(rows) * sizeof(int), &sp));
+  PAL_TRY(e->scratch(kWsSpectra, size_t(rows) * pl->spec_stride() * sizeof(cd) + size_t(rows) * sizeof(int), &sp));
   cd* spectra = static_cast<cd*>(sp);
   int* nonzero = reinterpret_cast<int*>(spectra + size_t(rows) * pl->spec_stride());   // per frame row: any non-zero sample
   PAL_TRY(e->forward_spectra(*pl, d_frames, size_t(L), rows, L, spectra, nonzero));
@@ -223,7 +215,7 @@ static int all_pairs_dev(Engine* e, const double* d_frames, int B, int M, int L,
       e->blk_M = M;
     }
     void* tp = nullptr;
-    PAL_TRY(e->scratch(23, size_t(np) * sizeof(pal_pair_record), &tp));
+    PAL_TRY(e->scratch(kWsBlockTable, size_t(np) * sizeof(pal_pair_record), &tp));
     PAL_TRY(e->pair_correlations(*pl, spectra, rows, e->quads_blk, np, L, *prm, static_cast<pal_pair_record*>(tp), nullptr, nullptr, nonzero));
     k_scatter_records<<<dim3(unsigned((np + 255) / 256)), dim3(256), 0, e->stream>>>(static_cast<const pal_pair_record*>(tp), e->perm_blk, np, d_table);
     return e->check(hipGetLastError(), "k_scatter_records");
@@ -252,9 +244,9 @@ static int pairs_host(Engine* e, const double* rows_in, int R, int L, const int3
   for (int64_t k = 0; k < 2 * P; ++k)
     if (pairs[k] < 0 || pairs[k] >= R) return e->fail(PAL_ERR_INVALID, "pair %lld references row outside 0..%d", (long long)(k / 2), R - 1);
   void *df = nullptr, *dt = nullptr, *dp = nullptr;
-  PAL_TRY(e->scratch(4, size_t(R) * L * sizeof(double), &df));
-  PAL_TRY(e->scratch(5, size_t(P) * sizeof(pal_pair_record), &dt));
-  PAL_TRY(e->scratch(15, size_t(2 * P) * sizeof(int32_t), &dp));
+  PAL_TRY(e->scratch(kWsStageIn, size_t(R) * L * sizeof(double), &df));
+  PAL_TRY(e->scratch(kWsStageTable, size_t(P) * sizeof(pal_pair_record), &dt));
+  PAL_TRY(e->scratch(kWsStagePairs, size_t(2 * P) * sizeof(int32_t), &dp));
   PAL_TRY(e->check(hipMemcpyAsync(df, rows_in, size_t(R) * L * sizeof(double), hipMemcpyHostToDevice, e->stream), "rows upload"));
   PAL_TRY(e->check(hipMemcpyAsync(dp, pairs, size_t(2 * P) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream), "pairs upload"));
   PAL_TRY(e->check(hipStreamSynchronize(e->stream), "upload sync"));
@@ -451,9 +443,9 @@ int pal_gcc_phat_all_pairs(pal_handle h, const double* frames, int B, int M, int
   const size_t fbytes = size_t(B) * M * L * sizeof(double);
   const int64_t np = int64_t(B) * M * (M - 1) / 2;
   void *df = nullptr, *dt = nullptr, *dc = nullptr;
-  PAL_TRY(e->scratch(4, fbytes, &df));
-  PAL_TRY(e->scratch(5, size_t(np) * sizeof(pal_pair_record), &dt));
-  if (corr) PAL_TRY(e->scratch(6, size_t(np) * size_t(2 * L - 1) * sizeof(double), &dc));
+  PAL_TRY(e->scratch(kWsStageIn, fbytes, &df));
+  PAL_TRY(e->scratch(kWsStageTable, size_t(np) * sizeof(pal_pair_record), &dt));
+  if (corr) PAL_TRY(e->scratch(kWsStageOut, size_t(np) * size_t(2 * L - 1) * sizeof(double), &dc));
   PAL_TRY(e->check(hipMemcpyAsync(df, frames, fbytes, hipMemcpyHostToDevice, e->stream), "frames upload"));
   PAL_TRY(all_pairs_dev(e, static_cast<const double*>(df), B, M, L, prm, static_cast<pal_pair_record*>(dt),
                         static_cast<double*>(dc)));
@@ -502,9 +494,9 @@ int pal_bootstrap_peaks(pal_handle h, const double* rows, int R, int L, const in
     if (pairs[k] < 0 || pairs[k] >= R) return e->fail(PAL_ERR_INVALID, "pair %lld references row outside 0..%d", (long long)(k / 2), R - 1);
   const size_t pbytes = size_t(P) * size_t(num_bootstrap) * sizeof(double);
   void *df = nullptr, *dp = nullptr, *dk = nullptr;
-  PAL_TRY(e->scratch(4, size_t(R) * L * sizeof(double), &df));
-  PAL_TRY(e->scratch(15, size_t(2 * P) * sizeof(int32_t), &dp));
-  PAL_TRY(e->scratch(13, pbytes, &dk));
+  PAL_TRY(e->scratch(kWsStageIn, size_t(R) * L * sizeof(double), &df));
+  PAL_TRY(e->scratch(kWsStagePairs, size_t(2 * P) * sizeof(int32_t), &dp));
+  PAL_TRY(e->scratch(kWsBootPeaks, pbytes, &dk));
   PAL_TRY(e->check(hipMemcpyAsync(df, rows, size_t(R) * L * sizeof(double), hipMemcpyHostToDevice, e->stream), "rows upload"));
   PAL_TRY(e->check(hipMemcpyAsync(dp, pairs, size_t(2 * P) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream), "pairs upload"));
   PAL_TRY(e->bootstrap_peaks_dev(static_cast<const double*>(df), R, L, static_cast<const int32_t*>(dp), P, num_bootstrap, mode, block_size,
@@ -522,11 +514,11 @@ static int single_pair(Engine* e, const double* sig1, int n1, const double* sig2
   Plan* pl = nullptr;
   PAL_TRY(e->get_plan(n, lin, n, &pl));
   void *df = nullptr, *sp = nullptr, *dc = nullptr, *dt = nullptr, *qp = nullptr, *dk = nullptr;
-  PAL_TRY(e->scratch(4, size_t(2) * lin * sizeof(double), &df));
-  PAL_TRY(e->scratch(2, size_t(2) * pl->spec_stride() * sizeof(cd), &sp));
-  PAL_TRY(e->scratch(6, size_t(n) * sizeof(double), &dc));
-  PAL_TRY(e->scratch(5, sizeof(pal_pair_record) + PAL_MAX_PEAKS * sizeof(int32_t), &dt));
-  PAL_TRY(e->scratch(3, sizeof(int4), &qp));
+  PAL_TRY(e->scratch(kWsStageIn, size_t(2) * lin * sizeof(double), &df));
+  PAL_TRY(e->scratch(kWsSpectra, size_t(2) * pl->spec_stride() * sizeof(cd), &sp));
+  PAL_TRY(e->scratch(kWsStageOut, size_t(n) * sizeof(double), &dc));
+  PAL_TRY(e->scratch(kWsStageTable, sizeof(pal_pair_record) + PAL_MAX_PEAKS * sizeof(int32_t), &dt));
+  PAL_TRY(e->scratch(kWsQuads, sizeof(int4), &qp));
   dk = static_cast<char*>(dt) + sizeof(pal_pair_record);
   double* d = static_cast<double*>(df);
   PAL_TRY(e->check(hipMemcpyAsync(d, sig1, size_t(n1) * sizeof(double), hipMemcpyHostToDevice, e->stream), "sig1 upload"));
@@ -566,12 +558,12 @@ int pal_corr_metrics(pal_handle h, const double* corr, int n, pal_pair_record* r
   ENGINE(h);
   if (!corr || !rec || n < 1) return e->fail(PAL_ERR_INVALID, "bad correlation row");
   void *dc = nullptr, *dt = nullptr;
-  PAL_TRY(e->scratch(6, size_t(n) * sizeof(double), &dc));
-  PAL_TRY(e->scratch(5, sizeof(pal_pair_record), &dt));
+  PAL_TRY(e->scratch(kWsStageOut, size_t(n) * sizeof(double), &dc));
+  PAL_TRY(e->scratch(kWsStageTable, sizeof(pal_pair_record), &dt));
   PAL_TRY(e->check(hipMemcpyAsync(dc, corr, size_t(n) * sizeof(double), hipMemcpyHostToDevice, e->stream), "corr upload"));
   pal_phat_params p{};
   p.fs = 1; p.threshold_method = -1; p.peak_distance = 1; p.num_peaks = 1; p.max_expected_delay = NAN;
-  PAL_TRY(e->peaks(static_cast<const double*>(dc), size_t(n), 1, n, 1, p, static_cast<pal_pair_record*>(dt), nullptr, e->stream));
+  PAL_TRY(e->peaks(static_cast<const double*>(dc), size_t(n), 1, n, 1, p, static_cast<pal_pair_record*>(dt), nullptr, 0));   // slot 0: on `stream`
   PAL_TRY(e->check(hipMemcpyAsync(rec, dt, sizeof(pal_pair_record), hipMemcpyDeviceToHost, e->stream), "record download"));
   return pal_synchronize(h);
 }

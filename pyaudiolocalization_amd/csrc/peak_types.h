@@ -8,6 +8,21 @@ namespace pal {
 
 constexpr int kList = 16384;      // capacity of a row's bracket list in global memory (doubles)
 
+// The engine's status words (Engine::status_words): written by kernels, read and cleared by pal_synchronize.  Words 1 and 3 .. 13
+// are diagnostics, reported under PAL_DEBUG_FALLBACK only.
+enum StatusWord : int {
+  kStOverflow = 0,        // peak selection: a suppression chain exceeded the on-chip memo / stack (PAL_ERR_INTERNAL)
+  kStRadixFallback = 1,   // rows whose median needed the radix select
+  kStInput = 2,           // input problems found by device-side checks (PAL_ERR_INVALID): StatusInputBit
+  kStExactMedian = 3,     // rows that needed the exact median (a threshold comparison inside the histogram interval)
+  kStFlagged = 4,         // rows of a finishing pass that went through the stored-row path ...
+  kStWhy = 5,             // ... and why: kStWhyCount words, 5 .. 12 (bit b of pfa_cols_fin.h's `why` -> word kStWhy + b)
+  kStGaveUp = 13,         // bounded waits of the finishing pass given up
+  kStatusWords = 16
+};
+constexpr int kStWhyCount = 8;
+enum StatusInputBit : int { kStInputNonFinite = 1, kStInputBadRow = 2 };   // a NaN or an infinity in a frame; a pair list references a row outside the frame batch
+
 struct RowPre {                          // pivot launch -> the other two
   double k0, ka;                         // ~ mean(x), ~ mean(|x|): shifts of the one-pass sums
   double lo, hi;                         // pivots around the median of |x| (0 / inf when no median is needed)

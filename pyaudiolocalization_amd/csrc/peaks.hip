@@ -1191,14 +1191,14 @@ __device__ __forceinline__ void finish_row(const PeakArgs& a, pal_pair_record* t
               ok = interval_select(s, tid, c, n, b1lo, b1hi, rin1, m0);
               if (ok) { m1 = m0; if (r2 != r1) ok = interval_select(s, tid, c, n, b2lo, b2hi, rin2, m1); }
             }
-            if (tid == 0) atomicAdd(status + (ok ? 3 : 1), 1);       // diagnostics: rows that needed the exact median / the radix select
+            if (tid == 0) atomicAdd(status + (ok ? kStExactMedian : kStRadixFallback), 1);       // diagnostics: rows that needed the exact median / the radix select
           } else {
             const int cnt = a.gcount[row];
             const double* list = a.glist + size_t(row) * kList;
             ok = cnt >= 0 && cnt <= kList && (long long)r1 >= below && (long long)r2 < below + cnt;
             if (ok) ok = list_select(s, tid, list, cnt, unsigned(r1 - below), lo, hi, m0);
             if (ok) { m1 = m0; if (r2 != r1) ok = list_select(s, tid, list, cnt, unsigned(r2 - below), lo, hi, m1); }
-            if (!ok && tid == 0) atomicAdd(status + 1, 1);           // diagnostics: rows that needed the slow exact select
+            if (!ok && tid == 0) atomicAdd(status + kStRadixFallback, 1);           // diagnostics: rows that needed the slow exact select
           }
           if (!ok) {                                                 // pivots / windows missed or a list overflowed: exact radix select
             m0 = radix_select(c, n, tid, s, r1);
@@ -1272,7 +1272,7 @@ __device__ __forceinline__ void finish_row(const PeakArgs& a, pal_pair_record* t
     table[row] = r;
     if (ksel_multi)
       for (int k = 0; k < PAL_MAX_PEAKS; ++k) ksel_multi[size_t(row) * PAL_MAX_PEAKS + k] = k < count ? s.sel_pos[k] : -1;
-    if (overflow) atomicOr(status, 1);
+    if (overflow) atomicOr(status + kStOverflow, 1);
   }
 }
 
@@ -1283,14 +1283,8 @@ __global__ __launch_bounds__(kT, 4) void k_peak_finish(PeakArgs a, pal_pair_reco
 
 }  // namespace
 
-static int* g_status_dev(Engine* e) {
-  void* p = nullptr;
-  if (e->scratch(7, 64, &p) != PAL_OK) return nullptr;
-  return static_cast<int*>(p);
-}
-
 int Engine::peaks_setup(const double* corr, size_t stride, int rows, int n, int n2, const pal_phat_params& prm, int blocks, int grid_n2,
-                        hipStream_t on, PeakArgs& a) {
+                        int slot, PeakArgs& a) {
   const bool metrics_only = prm.threshold_method < 0;
   if (!metrics_only) {
     if (prm.num_peaks < 1 || prm.num_peaks > PAL_MAX_PEAKS) return fail(PAL_ERR_INVALID, "num_peaks %d outside 1..%d", prm.num_peaks, PAL_MAX_PEAKS);
@@ -1325,9 +1319,8 @@ int Engine::peaks_setup(const double* corr, size_t stride, int rows, int n, int 
   const size_t list_bytes = a.local_pivots ? size_t(rows) * a.splits * sizeof(BlockHist) : (a.method == 0 ? size_t(rows) * kList * sizeof(double) : 0);
   const size_t off_bits = (off_list + list_bytes + 127) & ~size_t(127);
   const size_t total = off_bits + (corr ? size_t(rows) * 2 * ((size_t(n) + 31) / 32) * sizeof(unsigned) : 0);   // (bitmaps only where rows are stored)
-  void* sp = nullptr;
-  PAL_TRY(scratch(on == stream2 ? 9 : (on == stream3 ? 12 : 8), total, &sp));
-  char* base = static_cast<char*>(sp);
+  char* base = nullptr;
+  PAL_TRY(scratch(peak_scratch_slot(slot), total, &base));
   a.gcount = reinterpret_cast<int*>(base);
   a.pre = reinterpret_cast<RowPre*>(base + off_pre);
   a.parts = reinterpret_cast<Partial*>(base + off_parts);
@@ -1342,10 +1335,11 @@ int Engine::peaks_setup(const double* corr, size_t stride, int rows, int n, int 
   return PAL_OK;
 }
 
-int Engine::peaks_finish(PeakArgs& a, int rows, pal_pair_record* table, int32_t* ksel_multi, hipStream_t on) {
+int Engine::peaks_finish(PeakArgs& a, int rows, pal_pair_record* table, int32_t* ksel_multi, int slot) {
   const bool metrics_only = a.method < 0;
-  int* status = g_status_dev(this);
-  if (!status) return fail(PAL_ERR_NOMEM, "status word");
+  const hipStream_t on = stream_of(slot);
+  int* status = nullptr;
+  PAL_TRY(status_words(&status));
   {
     ProfScope ps(this, metrics_only ? "k_peak_finish(metrics)" : "k_peak_finish", on);
     if (a.local_pivots) k_peak_finish<true><<<dim3(rows), dim3(kT), 0, on>>>(a, table, ksel_multi, status);
@@ -1356,10 +1350,11 @@ int Engine::peaks_finish(PeakArgs& a, int rows, pal_pair_record* table, int32_t*
 }
 
 int Engine::peaks(const double* corr, size_t stride, int rows, int n, int n2, const pal_phat_params& prm,
-                  pal_pair_record* table, int32_t* ksel_multi, hipStream_t on) {
+                  pal_pair_record* table, int32_t* ksel_multi, int slot) {
   if (rows <= 0) return PAL_OK;
+  const hipStream_t on = stream_of(slot);
   PeakArgs a;
-  PAL_TRY(peaks_setup(corr, stride, rows, n, n2, prm, 0, 0, on, a));
+  PAL_TRY(peaks_setup(corr, stride, rows, n, n2, prm, 0, 0, slot, a));
   {
     ProfScope ps(this, "k_peak_pivots", on);
     k_peak_pivots<<<dim3(rows), dim3(kT), 0, on>>>(a);
@@ -1370,7 +1365,7 @@ int Engine::peaks(const double* corr, size_t stride, int rows, int n, int n2, co
     k_peak_stream<<<dim3(unsigned(rows) * unsigned(a.splits)), dim3(kTS), 0, on>>>(a);
     PAL_HIP(hipGetLastError());
   }
-  return peaks_finish(a, rows, table, ksel_multi, on);
+  return peaks_finish(a, rows, table, ksel_multi, slot);
 }
 
 }  // namespace pal

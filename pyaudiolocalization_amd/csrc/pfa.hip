@@ -303,9 +303,8 @@ bool Engine::pfa_forward_applies(const Plan& pl, int len) const {
 
 int Engine::pfa_forward_spectra(Plan& pl, const double* frames, size_t frame_stride, int rows, int len, cd* spectra) {
   const Pfa& f = pl.pfa;
-  void* wsp = nullptr;
-  PAL_TRY(scratch(0, size_t(chunk) * size_t(pl.n) * sizeof(cd), &wsp));
-  cd* Y = static_cast<cd*>(wsp);
+  cd* Y = nullptr;
+  PAL_TRY(scratch(kWsWork, size_t(chunk) * size_t(pl.n) * sizeof(cd), &Y));
   for (int r0 = 0; r0 < rows; r0 += 2 * chunk) {
     const int R = rows - r0 < 2 * chunk ? rows - r0 : 2 * chunk;   // frames of this group, two per transform
     const int G = (R + 1) / 2;
@@ -327,25 +326,19 @@ int Engine::pfa_forward_spectra(Plan& pl, const double* frames, size_t frame_str
   return PAL_OK;
 }
 
-// the fused column pass applies when one workgroup covers every output index (nch <= 4 chunks of kPfaTC: N1 <= 89)
-bool Engine::pfa_can_fuse(const Plan& pl) const {
-  const Pfa& f = pl.pfa;
-  return fuse_peaks && f.on() && f.nch >= 1 && f.nch <= 4 && f.n2 >= 3;
-}
-
 // row pass, column pass + streaming statistics (every column block publishes a histogram window around its median),
 // finish: the peak selection of one launch group without a pivot launch, without bracket lists and without the separate
 // read of its correlation rows (pfa_cols_stats.h)
 int Engine::pfa_pair_group_fused(const Plan& pl, const cd* permuted, const int4* quads, int G, int rows, cd* Y, double* corr, size_t stride,
                                  const int* zero_rows, const pal_phat_params& prm, int n2, pal_pair_record* table, int32_t* ksel_multi,
-                                 hipStream_t on) {
+                                 int slot) {
   const Pfa& f = pl.pfa;
+  const hipStream_t on = stream_of(slot);
   // short column DFTs (one chunk: N1 <= 23): the four wavefronts of a workgroup take four neighbouring strips
   const bool shortcols = f.nch <= 1;
-  const int per_blk = shortcols ? kColsOwn * 4 : kColsOwn;
-  const int nblk = (f.n2 + per_blk - 1) / per_blk;
+  const int nblk = fin_blocks(f.n2, f.nch);
   PeakArgs a;
-  PAL_TRY(peaks_setup(corr, stride, rows, pl.n, n2, prm, nblk, f.n2, on, a));
+  PAL_TRY(peaks_setup(corr, stride, rows, pl.n, n2, prm, nblk, f.n2, slot, a));
   PAL_TRY(pfa_rows(pl, permuted, quads, G, Y, on));
   {
     ProfScope ps(this, "k_pfa_cols_stats", on);
@@ -365,38 +358,10 @@ int Engine::pfa_pair_group_fused(const Plan& pl, const cd* permuted, const int4*
 #undef PAL_COLS_STATS
     PAL_HIP(hipGetLastError());
   }
-  return peaks_finish(a, rows, table, ksel_multi, on);
+  return peaks_finish(a, rows, table, ksel_multi, slot);
 }
-
 
 // ---- the column pass that finishes the rows itself (pfa_cols_fin.h, pfa_fin_lean.h): no correlation rows in HBM, no finish launch ----
-
-// the threshold needs no histograms: 'adaptive', or 'median' with a multiplier in 0 .. 2 (pfa_cols_fin.h fin_decide bounds the median)
-static bool nohist(const pal_phat_params& prm) {
-  return prm.threshold_method > 0 || (prm.threshold_multiplier >= 0 && prm.threshold_multiplier <= 2.0);
-}
-
-// One peak per row (main.py:204), the caller does not ask for `corr`, and the grid's rows have at least 256 columns.  Which column
-// forms take it is decided by measurement over the sync-padded lengths (see below); the other plans keep their rows in HBM - with
-// the same per-wavefront statistics where the grid is large enough (pfa_can_lean_store), else with round 2's statistics.
-bool Engine::pfa_can_finish(const Plan& pl, const pal_phat_params& prm) const {
-  const Pfa& f = pl.pfa;
-  // Measured over L = 44100 ... 44299 with the per-wavefront statistics of pfa_fin_lean.h (profiles/r03_c_length_sweep_dense_fin.csv
-  // against ..._default.csv): the pass wins with Rader-89 columns (+10 %), with two or four chunks of output indices (+3 ... +12 %, +4 %)
-  // and with short columns beside row tiles of up to 8192 points (+8 %); three chunks leave the fourth wavefront idle (-2 %), and
-  // beside the 16384-point row tiles it is a wash
-  bool cols_ok = f.r89 != nullptr || (f.nch >= 2 && f.nch <= 4) || (f.nch <= 1 && f.lm <= 13);
-  // ... on grids of at least twelve column blocks per transform (N2 >= 683; strips: N2 >= 2729): with fewer, a launch group is one or
-  // two rounds of blocks and the pass is the sum of one block's latencies - the stream chain's lengths (n = 24 000 ... 24 500:
-  // 59 x 407, seven blocks) ran 534 frames/s with the pass and 579 without
-  const int nblk = (f.n2 + (f.nch <= 1 ? 4 : 1) * kColsOwn - 1) / ((f.nch <= 1 ? 4 : 1) * kColsOwn);
-  if (!f.r89 && nblk < 12) cols_ok = false;
-  // (five and six chunks, N1 up to 133, are not finished here: pfa_can_fuse stops at four.  Tried with five- /
-  // six-wavefront blocks: correct, but C5 ran 2.53 against 2.58 M pairs/s with it - 960 blocks are one round of the machine, every
-  // wavefront is in the same phase at the same time and the pass (160 us) is the sum of its latencies, where the separate launches
-  // (70 + 18 + 31 + 32) overlap.  Their stored rows take k_rows_lean)
-  return fin_cols && pfa_can_fuse(pl) && prm.num_peaks == 1 && f.n2 >= 256 && cols_ok;
-}
 
 // The blocks of a finishing pass wait for their siblings (pfa_cols_fin.h).  ONE such launch is deadlock-free (its workgroups are
 // dispatched in order and siblings are adjacent), but two of them on different streams can fill every workgroup slot of the
@@ -418,21 +383,15 @@ int Engine::fin_done(hipStream_t on) {
 // arguments and scratch of one launch of the finishing pass, nblk blocks per transform; `grid_rows`: the rows of the grid whose first
 // and last columns go to the finishing wavefront (the prime-factor grid's N1; k_rows_lean has no such columns: 1)
 int Engine::fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, const pal_phat_params& prm, int n2, pal_pair_record* table,
-                      int* need, int slot, hipStream_t on, PeakArgs& a, FinArgs& fa, unsigned& nwg, int G) {
+                      int* need, int slot, PeakArgs& a, FinArgs& fa, unsigned& nwg, int G) {
   const int n = pl.n;
-  PAL_TRY(peaks_setup(nullptr, 0, rows, n, n2, prm, nblk, 0, on, a));
+  PAL_TRY(peaks_setup(nullptr, 0, rows, n, n2, prm, nblk, 0, slot, a));
   // per-stream scratch of the finishing pass: [done words G x blocks | emax | parts | edge] (fin_scratch.h)
   // (`done` words and FinPartial entries: room for one per WAVEFRONT of a block, pfa_fin_lean.h)
   const FinLayout lay = fin_layout(pair_group(n), nblk, grid_rows);
-  void* sp = nullptr;
-  PAL_TRY(scratch(16 + slot, lay.total, &sp));
-  char* base = static_cast<char*>(sp);
-  int* status = nullptr;
-  {
-    void* stp = nullptr;
-    PAL_TRY(scratch(7, 64, &stp));
-    status = static_cast<int*>(stp);
-  }
+  char* base = nullptr;
+  PAL_TRY(scratch(fin_scratch_slot(slot), lay.total, &base));
+  PAL_TRY(status_words(&fa.status));
   fa.table = table;
   fa.need = need;
   fa.done = reinterpret_cast<unsigned*>(base);
@@ -442,9 +401,9 @@ int Engine::fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, const p
   key.gmax = pair_group(n);
   key.nblk = nblk;
   key.grid_rows = grid_rows;
-  key.block = ws_bytes[16 + slot];
+  key.block = ws_bytes[fin_scratch_slot(slot)];
   if (fin_must_zero(fin_key[slot], key, fin_epoch[slot], fin_wrap)) {
-    PAL_HIP(hipMemsetAsync(sp, 0, ws_bytes[16 + slot], on));
+    PAL_HIP(hipMemsetAsync(base, 0, key.block, stream_of(slot)));
     fin_key[slot] = key;
     fin_epoch[slot] = 0;
   }
@@ -453,7 +412,6 @@ int Engine::fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, const p
   fa.parts = reinterpret_cast<FinPartial*>(base + lay.off_parts);
   fa.edge = reinterpret_cast<double*>(base + lay.off_edge);
   fa.giveup = fin_giveup;
-  fa.status = status;
   // the lag window |m - (n2 - 1)| / fs <= max_expected_delay (utils.py:163) as sample indices, with the reference's arithmetic
   fa.pw = 1;
   fa.corr = nullptr;
@@ -477,63 +435,43 @@ int Engine::fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, const p
       fa.win_hi = int(hi > n - 2 ? n - 2 : hi);
     }
   }
-  fa.cheb = a.method == 0 && nohist(prm) ? 1 : 0;
+  fa.cheb = a.method == 0 && nohist(prm.threshold_method, prm.threshold_multiplier) ? 1 : 0;
   nwg = 8u * unsigned((G + 7) / 8) * unsigned(nblk);
   return PAL_OK;
 }
 
-// Statistics of rows that are already in HBM, any route (k_rows_lean): one launch instead of pivots + stream + finish where one peak per
-// row is asked for and the threshold needs no histograms; flagged rows are resolved at the end of the call.
-bool Engine::rows_can_lean(const Plan& pl, const pal_phat_params& prm) const {
-  // Measured: rows of 12 013 ... 24 013 samples +2 ... +8 % (C5 2.58 -> 2.87 M pairs/s: 66 us per group against 18 + 31 + 32), rows of
-  // 88 201 ... 88 367 -3 ... +1 %, C4's 191 999 the same: long rows keep the three launches (their stream pass runs at the HBM rate)
-  return rows_lean && fin_cols && prm.num_peaks == 1 && nohist(prm) && pl.nout == pl.n && pl.n >= 4096 && pl.n <= 50000;
-}
-
+// Statistics of rows that are already in HBM, any route (k_rows_lean, RouteStats::kRowsLean of pair_route.h)
 int Engine::rows_lean_group(const Plan& pl, const double* corr, size_t stride, int G, int rows, const pal_phat_params& prm, int n2,
-                            pal_pair_record* table, int* need, int slot, hipStream_t on) {
+                            pal_pair_record* table, int* need, int slot) {
   constexpr int NS = 22;
+  const hipStream_t on = stream_of(slot);
   const int chunks = (pl.n + kColsOwn - 1) / kColsOwn;
   const int nblk = (chunks + 4 * NS - 1) / (4 * NS);
   PeakArgs a;
   FinArgs fa;
   unsigned nwg = 0;
-  PAL_TRY(fin_setup(pl, rows, nblk, 1, prm, n2, table, need, slot, on, a, fa, nwg, G));
+  PAL_TRY(fin_setup(pl, rows, nblk, 1, prm, n2, table, need, slot, a, fa, nwg, G));
   fa.pw = 4;
   fa.corr = const_cast<double*>(corr);
   fa.stride = stride;
-  fa.store_rows = 0;
   ProfScope ps(this, "k_rows_lean", on);
   k_rows_lean<NS><<<dim3(nwg), dim3(256), 0, on>>>(corr, stride, G, nblk, a, fa, rows);
   PAL_HIP(hipGetLastError());
   return PAL_OK;
 }
 
-// The same pass with the correlation rows stored as well (the caller wants them, or the plan has no finishing form that pays):
-// per-wavefront statistics, no sibling polls, the finisher reads the SNR window from the stored row; flagged rows are resolved at the
-// end of the call like the finishing pass's.  Replaces pfa_cols_stats.h / the three statistics launches + k_peak_finish where one
-// peak per row is asked for and the threshold needs no histograms.
-bool Engine::pfa_can_lean_store(const Plan& pl, const pal_phat_params& prm) const {
-  const Pfa& f = pl.pfa;
-  // Several rounds of column blocks per launch group, or the pass is the sum of one block's latencies: C5 (103 x 233: four blocks per
-  // transform, 960 per group, one round) measured 2.32 against 2.60 M pairs/s with it; C3 (7 x 6857: 28 blocks) 1.16 against 1.08,
-  // C2 (17 x 5647: 23 blocks) 0.422 against 0.417
-  const int nblk = (f.n2 + (f.nch <= 1 ? 4 : 1) * kColsOwn - 1) / ((f.nch <= 1 ? 4 : 1) * kColsOwn);
-  // (five and six chunks, N1 = 91 ... 127 beside 700 - 970 columns: 0.63 - 0.66 against 0.69 - 0.71 M with it: they keep the three statistics launches)
-  return lean_store && fin_cols && fuse_peaks && f.on() && f.nch >= 1 && f.nch <= 4 && nblk >= 12 && prm.num_peaks == 1 && nohist(prm);
-}
-
+// The finishing column pass (RouteTransform::kFinish), and the same pass with the correlation rows stored as well (kLeanStore: `corr`)
 int Engine::pfa_pair_group_fin(const Plan& pl, const cd* permuted, const int4* quads, int G, int rows, cd* Y, const int* zero_rows,
-                               const pal_phat_params& prm, int n2, pal_pair_record* table, int* need, int slot, hipStream_t on,
+                               const pal_phat_params& prm, int n2, pal_pair_record* table, int* need, int slot,
                                double* corr, size_t stride) {
   const Pfa& f = pl.pfa;
-  if (f.nch > 4) return fail(PAL_ERR_INTERNAL, "finishing column pass with %d chunks", f.nch);   // (pfa_can_finish never asks for it)
+  const hipStream_t on = stream_of(slot);
   const bool shortcols = f.nch <= 1;                           // short column DFTs (N1 <= 23): the four wavefronts of a block are four strips
-  const int nblk = (f.n2 + (shortcols ? 4 : 1) * kColsOwn - 1) / ((shortcols ? 4 : 1) * kColsOwn);
+  const int nblk = fin_blocks(f.n2, f.nch);
   PeakArgs a;
   FinArgs fa;
   unsigned nwg = 0;
-  PAL_TRY(fin_setup(pl, rows, nblk, f.n1, prm, n2, table, need, slot, on, a, fa, nwg, G));
+  PAL_TRY(fin_setup(pl, rows, nblk, f.n1, prm, n2, table, need, slot, a, fa, nwg, G));
   fa.corr = corr;
   fa.stride = stride;
   fa.store_rows = corr ? 1 : 0;

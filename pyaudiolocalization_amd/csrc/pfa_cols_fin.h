@@ -66,7 +66,7 @@ struct FinArgs {
   unsigned epoch;                 // number of this launch on its stream (> 0; the scratch starts zeroed): stale entries fail the comparison, nothing is reset
   int giveup;                     // 1 (PAL_DEBUG_FIN_GIVEUP): every bounded wait gives up without polling - the rows take the stored-row path
   FinPartial* parts;              // [rows][S]
-  int* status;                    // engine status words (bit 2 of word 0: a wait timed out; word 4: flagged rows)
+  int* status;                    // engine status words (peak_types.h: kStFlagged rows, kStWhy + reason, kStGaveUp waits)
   int win_lo, win_hi;             // lag window as sample indices, |m - (n2 - 1)| / fs <= max_expected_delay (win_lo > win_hi: empty)
   int windowed;
   int pw;                         // FinPartial entries and `done` words per column block: 1, or one per wavefront (pfa_fin_lean.h)
@@ -237,9 +237,9 @@ __device__ __forceinline__ void fin_decide(const PeakArgs& pa, const FinArgs& fa
   if (writer) {
     fa.need[row] = flag ? 1 : 0;
     if (flag) {
-      atomicAdd(fa.status + 4, 1);
-      for (int b = 0; b < 8; ++b)
-        if (why >> b & 1) atomicAdd(fa.status + 5 + b, 1);
+      atomicAdd(fa.status + kStFlagged, 1);
+      for (int b = 0; b < kStWhyCount; ++b)
+        if (why >> b & 1) atomicAdd(fa.status + kStWhy + b, 1);
     } else {
       pal_pair_record r;
       r.k_sel = sel; r.branch = branch; r.k_argmax = imax; r.n_sel = 1;
@@ -777,7 +777,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
       if (!late && i >= 0 && i < n && (bi < 0 || arg_better<0>(v, i, bv, bi))) { bv = v; bi = i; }
     }
     const bool gave_up = __ballot(late) != 0;
-    if (gave_up && lane == 0) { s_flag = 1; atomicAdd(fa.status + 13, 1); }
+    if (gave_up && lane == 0) { s_flag = 1; atomicAdd(fa.status + kStGaveUp, 1); }
     wave_arg63(bv, bi, [](double v1, int i1, double v2, int i2) { return arg_better<0>(v1, i1, v2, i2); });
     if (lane == 63) s_imax[wave] = bi;
   }
@@ -845,7 +845,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
       }
     }
     if (__syncthreads_or(late ? 1 : 0)) {                     // the siblings' results are not there: both rows go through the stored-row path
-      if (tid < 2 && 2 * g + tid < rows) { fa.need[2 * g + tid] = 1; atomicAdd(fa.status + 4, 1); atomicAdd(fa.status + 13, 1); }
+      if (tid < 2 && 2 * g + tid < rows) { fa.need[2 * g + tid] = 1; atomicAdd(fa.status + kStFlagged, 1); atomicAdd(fa.status + kStGaveUp, 1); }
       return;
     }
   }

@@ -38,8 +38,7 @@
 
 namespace pal {
 
-constexpr int kColsOwn = 62;      // columns a workgroup of the fused column pass owns (64 lanes - two border lanes)
-
+// (kColsOwn, the columns a workgroup owns: pair_route.h, which counts the column blocks with it)
 struct ColsWaveResult {           // one wavefront's share of a row segment
   double vmax, vmin, hb, s1, s2, a1, plat;
   int imax, mb, pad0, pad1;

@@ -325,7 +325,7 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
     });
     w1[r] = u1; w2[r] = u2;
   }
-  if (gave_up && lane == 0) atomicAdd(fa.status + 13, 1);
+  if (gave_up && lane == 0) atomicAdd(fa.status + kStGaveUp, 1);
 
   // ---- the window sums' butterfly; lane r publishes row r's results, then the wavefront's `done` word follows
   {
@@ -440,7 +440,7 @@ __device__ __forceinline__ void fin_rows_wave(const PeakArgs& pa, const FinArgs&
     }
   }
   if (__ballot(late)) {
-    if (lane < 2 && 2 * g + lane < rows) { fa.need[2 * g + lane] = 1; atomicAdd(fa.status + 4, 1); atomicAdd(fa.status + 13, 1); }
+    if (lane < 2 && 2 * g + lane < rows) { fa.need[2 * g + lane] = 1; atomicAdd(fa.status + kStFlagged, 1); atomicAdd(fa.status + kStGaveUp, 1); }
     return;
   }
 #pragma nounroll

@@ -365,12 +365,12 @@ static int simulate_dev(Engine* e, const double* d_base, int bases, int nbase, d
   Plan* pl = nullptr;
   PAL_TRY(e->get_plan(2 * N, nbase, N, &pl));
   void* sp = nullptr;
-  PAL_TRY(e->scratch(2, size_t(bases) * pl->H * sizeof(cd), &sp));
+  PAL_TRY(e->scratch(kWsSpectra, size_t(bases) * pl->H * sizeof(cd), &sp));
   cd* X = static_cast<cd*>(sp);
   PAL_TRY(e->forward_spectra(*pl, d_base, size_t(nbase), bases, nbase, X));
   const Conv& c = pl->inv;
   void* wsp = nullptr;
-  PAL_TRY(e->scratch(0, size_t(e->chunk) * c.M() * sizeof(cd), &wsp));
+  PAL_TRY(e->scratch(kWsWork, size_t(e->chunk) * c.M() * sizeof(cd), &wsp));
   cd* W = static_cast<cd*>(wsp);
   const int fl = int(0.01 * double(N));
   const double d = 1.0 / fs;
@@ -411,8 +411,8 @@ static int filtfilt_dev(Engine* e, const double* b, int nb, const double* a, int
   for (int q = 0; q < na; ++q) coef[K + q] = a[q] / a[0];
   for (int q = 0; q < K - 1; ++q) coef[2 * K + q] = zi[q];
   void *dc = nullptr, *dt = nullptr, *dd = nullptr;
-  PAL_TRY(e->scratch(3, coef.size() * sizeof(double) + (rows ? size_t(R) * sizeof(FiltRow) : 0), &dc));
-  PAL_TRY(e->scratch(1, size_t(R) * (N + 2 * edge) * sizeof(double), &dt));
+  PAL_TRY(e->scratch(kWsQuads, coef.size() * sizeof(double) + (rows ? size_t(R) * sizeof(FiltRow) : 0), &dc));
+  PAL_TRY(e->scratch(kWsCorr, size_t(R) * (N + 2 * edge) * sizeof(double), &dt));
   PAL_TRY(e->check(hipMemcpyAsync(dc, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, e->stream), "upload"));
   if (rows) {
     dd = static_cast<char*>(dc) + coef.size() * sizeof(double);
@@ -443,9 +443,9 @@ static int xcorr_dev(Engine* e, const double* x, int R, int N, int ref_idx, int3
   RefLoader rl{x + size_t(ref_idx) * N, N};
   PAL_TRY(launch_cols_fwd(e, c, 1, rl, c.chat));
   PAL_TRY(launch_rows(e, c, 1, c.chat, false, 1.0 / double(c.M())));
-  PAL_TRY(e->scratch(0, size_t(e->chunk) * c.M() * sizeof(cd), &wsp));
+  PAL_TRY(e->scratch(kWsWork, size_t(e->chunk) * c.M() * sizeof(cd), &wsp));
   const size_t stride = size_t(len) + 1;
-  PAL_TRY(e->scratch(1, size_t(2 * e->chunk) * stride * sizeof(double), &dcor));
+  PAL_TRY(e->scratch(kWsCorr, size_t(2 * e->chunk) * stride * sizeof(double), &dcor));
   const int ntr = (R + 1) / 2;
   for (int t0 = 0; t0 < ntr; t0 += e->chunk) {
     const int G = ntr - t0 < e->chunk ? ntr - t0 : e->chunk;
@@ -489,10 +489,10 @@ int pal_simulate_multipath(pal_handle h, const double* base, int B, int nbase, d
   void *db = nullptr, *dd = nullptr, *dg = nullptr, *dout = nullptr;
   int rc = PAL_OK;
   do {
-    if ((rc = e->scratch(4, size_t(B) * nbase * sizeof(double), &db)) != PAL_OK) break;
-    if ((rc = e->scratch(5, size_t(rows) * K * sizeof(double) * 2, &dd)) != PAL_OK) break;
+    if ((rc = e->scratch(kWsStageIn, size_t(B) * nbase * sizeof(double), &db)) != PAL_OK) break;
+    if ((rc = e->scratch(kWsStageTable, size_t(rows) * K * sizeof(double) * 2, &dd)) != PAL_OK) break;
     dg = static_cast<double*>(dd) + size_t(rows) * K;
-    if ((rc = e->scratch(6, size_t(rows) * out_len * sizeof(double), &dout)) != PAL_OK) break;
+    if ((rc = e->scratch(kWsStageOut, size_t(rows) * out_len * sizeof(double), &dout)) != PAL_OK) break;
     if ((rc = e->check(hipMemcpyAsync(db, base, size_t(B) * nbase * sizeof(double), hipMemcpyHostToDevice, e->stream), "upload")) != PAL_OK) break;
     if ((rc = e->check(hipMemcpyAsync(dd, delays, size_t(rows) * K * sizeof(double), hipMemcpyHostToDevice, e->stream), "upload")) != PAL_OK) break;
     // per-mic power-of-two rescale of the gains: k_gain_rescale, in place
@@ -513,9 +513,9 @@ int pal_fractional_delay(pal_handle h, const double* rows_in, int R, int N, cons
   ENGINE(h);
   if (!rows_in || !delays || !out || R < 1 || !(fs > 0)) return e->fail(PAL_ERR_INVALID, "bad fractional_delay arguments");
   void *db = nullptr, *dd = nullptr, *dout = nullptr;
-  PAL_TRY(e->scratch(4, size_t(R) * N * sizeof(double), &db));
-  PAL_TRY(e->scratch(5, size_t(R) * sizeof(double) * 2, &dd));
-  PAL_TRY(e->scratch(6, size_t(R) * N * sizeof(double), &dout));
+  PAL_TRY(e->scratch(kWsStageIn, size_t(R) * N * sizeof(double), &db));
+  PAL_TRY(e->scratch(kWsStageTable, size_t(R) * sizeof(double) * 2, &dd));
+  PAL_TRY(e->scratch(kWsStageOut, size_t(R) * N * sizeof(double), &dout));
   std::vector<double> ones(size_t(R), 1.0);
   double* dg = static_cast<double*>(dd) + R;
   UP(db, rows_in, size_t(R) * N * sizeof(double));
@@ -533,7 +533,7 @@ int pal_normalize_compress(pal_handle h, const double* rows_in, int R, int N, in
   ENGINE(h);
   if (!rows_in || !out || R < 1 || N < 1) return e->fail(PAL_ERR_INVALID, "bad normalize arguments");
   void* db = nullptr;
-  PAL_TRY(e->scratch(4, size_t(R) * N * sizeof(double), &db));
+  PAL_TRY(e->scratch(kWsStageIn, size_t(R) * N * sizeof(double), &db));
   UP(db, rows_in, size_t(R) * N * sizeof(double));
   {
     ProfScope ps(e, "k_norm_compress");
@@ -550,8 +550,8 @@ int pal_filtfilt(pal_handle h, const double* b, int nb, const double* a, int na,
   ENGINE(h);
   if (!rows_in || !out || R < 1 || N < 1) return e->fail(PAL_ERR_INVALID, "bad filtfilt arguments");
   void *dx = nullptr, *dy = nullptr;
-  PAL_TRY(e->scratch(4, size_t(R) * N * sizeof(double), &dx));
-  PAL_TRY(e->scratch(6, size_t(R) * N * sizeof(double), &dy));
+  PAL_TRY(e->scratch(kWsStageIn, size_t(R) * N * sizeof(double), &dx));
+  PAL_TRY(e->scratch(kWsStageOut, size_t(R) * N * sizeof(double), &dy));
   UP(dx, rows_in, size_t(R) * N * sizeof(double));
   PAL_TRY(filtfilt_dev(e, b, nb, a, na, zi, static_cast<double*>(dx), R, N, static_cast<double*>(dy)));
   DOWN(out, dy, size_t(R) * N * sizeof(double));
@@ -562,8 +562,8 @@ int pal_wiener3(pal_handle h, const double* rows_in, int R, int N, double* out) 
   ENGINE(h);
   if (!rows_in || !out || R < 1 || N < 1) return e->fail(PAL_ERR_INVALID, "bad wiener arguments");
   void *dx = nullptr, *dy = nullptr;
-  PAL_TRY(e->scratch(4, size_t(R) * N * sizeof(double), &dx));
-  PAL_TRY(e->scratch(6, size_t(R) * N * sizeof(double), &dy));
+  PAL_TRY(e->scratch(kWsStageIn, size_t(R) * N * sizeof(double), &dx));
+  PAL_TRY(e->scratch(kWsStageOut, size_t(R) * N * sizeof(double), &dy));
   UP(dx, rows_in, size_t(R) * N * sizeof(double));
   {
     ProfScope ps(e, "k_wiener3");
@@ -580,11 +580,11 @@ int pal_xcorr_vs_ref(pal_handle h, const double* rows_in, int R, int N, int ref_
   if (!rows_in || !kpk || !win5 || !pkabs || R < 1 || N < 1 || ref_idx < 0 || ref_idx >= R)
     return e->fail(PAL_ERR_INVALID, "bad xcorr arguments");
   void *dx = nullptr, *dres = nullptr;
-  PAL_TRY(e->scratch(4, size_t(R) * N * sizeof(double), &dx));
+  PAL_TRY(e->scratch(kWsStageIn, size_t(R) * N * sizeof(double), &dx));
   UP(dx, rows_in, size_t(R) * N * sizeof(double));
   // result block: kpk[R] (int32, padded to 16 bytes) | win5[R][5] | pkabs[R]
   const size_t off_d = (size_t(R) * sizeof(int32_t) + 15) & ~size_t(15);
-  PAL_TRY(e->scratch(5, off_d + size_t(R) * 6 * sizeof(double), &dres));
+  PAL_TRY(e->scratch(kWsStageTable, off_d + size_t(R) * 6 * sizeof(double), &dres));
   int32_t* dk = static_cast<int32_t*>(dres);
   double* dw = reinterpret_cast<double*>(static_cast<char*>(dres) + off_d);
   double* dp = dw + size_t(R) * 5;
@@ -610,7 +610,7 @@ int pal_simulate_multipath_dev(pal_handle h, const double* d_base, int B, int nb
   const int out_len = trim_len > 0 && trim_len < N ? trim_len : N;
   const int rows = B * M;
   void* dg = nullptr;
-  PAL_TRY(e->scratch(5, size_t(rows) * K * sizeof(double), &dg));
+  PAL_TRY(e->scratch(kWsStageTable, size_t(rows) * K * sizeof(double), &dg));
   k_gain_rescale<<<dim3((rows + 255) / 256), dim3(256), 0, e->stream>>>(d_gains, static_cast<double*>(dg), rows, K);
   PAL_TRY(e->check(hipGetLastError(), "k_gain_rescale"));
   return simulate_dev(e, d_base, B, nbase, fs, N, d_delays, static_cast<double*>(dg), rows, M, K, out_len, true, true, d_out);
@@ -652,7 +652,7 @@ int pal_row_energies_dev(pal_handle h, const double* d_rows, int R, int N, doubl
   ENGINE(h);
   if (!d_rows || !energy || R < 1 || N < 1) return e->fail(PAL_ERR_INVALID, "bad energy arguments");
   void* de = nullptr;
-  PAL_TRY(e->scratch(6, size_t(R) * sizeof(double), &de));
+  PAL_TRY(e->scratch(kWsStageOut, size_t(R) * sizeof(double), &de));
   k_row_energy<<<dim3(R), dim3(kLanes), 0, e->stream>>>(d_rows, size_t(N), N, static_cast<double*>(de));
   PAL_TRY(e->check(hipGetLastError(), "k_row_energy"));
   PAL_TRY(e->check(hipMemcpyAsync(energy, de, size_t(R) * sizeof(double), hipMemcpyDeviceToHost, e->stream), "download"));
@@ -666,7 +666,7 @@ int pal_sync_measure_dev(pal_handle h, const double* d_rows, int B, int M, int N
   const int R = B * M;
   // energies of every row -> the reference microphone of each frame (np.argmax: first of equals)
   void* de = nullptr;
-  PAL_TRY(e->scratch(6, size_t(R) * sizeof(double), &de));
+  PAL_TRY(e->scratch(kWsStageOut, size_t(R) * sizeof(double), &de));
   k_row_energy<<<dim3(R), dim3(kLanes), 0, e->stream>>>(d_rows, size_t(N), N, static_cast<double*>(de));
   PAL_TRY(e->check(hipGetLastError(), "k_row_energy"));
   std::vector<double> en(size_t(R), 0.0);
@@ -684,7 +684,7 @@ int pal_sync_measure_dev(pal_handle h, const double* d_rows, int B, int M, int N
   // result block for all frames: kpk[R] | win5[R][5] | pkabs[R]
   void* dres = nullptr;
   const size_t off_d = (size_t(R) * sizeof(int32_t) + 15) & ~size_t(15);
-  PAL_TRY(e->scratch(5, off_d + size_t(R) * 6 * sizeof(double), &dres));
+  PAL_TRY(e->scratch(kWsStageTable, off_d + size_t(R) * 6 * sizeof(double), &dres));
   int32_t* dk = static_cast<int32_t*>(dres);
   double* dw = reinterpret_cast<double*>(static_cast<char*>(dres) + off_d);
   double* dp = dw + size_t(R) * 5;
@@ -707,7 +707,7 @@ int pal_align_rows_dev(pal_handle h, const double* d_rows, int R, int N, const i
   for (int r = 0; r < R; ++r)
     if (pad_left[r] < 0 || pad_left[r] + N > Lout) return e->fail(PAL_ERR_INVALID, "pad %d of row %d does not fit %d samples", pad_left[r], r, Lout);
   void* dp = nullptr;
-  PAL_TRY(e->scratch(3, size_t(R) * sizeof(int32_t), &dp));
+  PAL_TRY(e->scratch(kWsQuads, size_t(R) * sizeof(int32_t), &dp));
   PAL_TRY(e->check(hipMemcpyAsync(dp, pad_left, size_t(R) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream), "upload"));
   PAL_TRY(e->check(hipStreamSynchronize(e->stream), "upload sync"));   // `pad_left` is host memory
   const unsigned gx = unsigned((Lout + 255) / 256 < 64 ? (Lout + 255) / 256 : 64);

@@ -154,6 +154,53 @@ int pal_bootstrap_peaks(pal_handle h, const double* rows, int R, int L, const in
 int pal_bootstrap_peaks_dev(pal_handle h, const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P,
                             int32_t num_bootstrap, int32_t mode, int32_t block_size, uint64_t seed, double* d_peaks);
 
+/* ---- position solve (main.py:233-298) on the device -------------------------------------------
+ * TDOA tables -> source positions, batched: per frame the reference's time delays (main.py:204-212), weights
+ * (utils.py:484-497), box (utils.py:364-382) and residuals (utils.py:384-405); then, instead of scikit-learn's clustered
+ * starts and SciPy's trust-region solver, a fixed start list (0: the mean microphone position, 1 .. grid^3: the cell centres
+ * of a grid over the box, x slowest, then n_extra caller starts clipped to the box) and one bounded Levenberg-Marquardt
+ * iteration per (frame, start) in float64.  The lowest cost among the starts that ended inside a stop rule wins, exact ties
+ * to the lowest start index.  pyaudiolocalization_amd/solve.py states the algorithm step by step (the kernels differ from it
+ * only in the order of the sums over the pairs); results do not depend on which other frames share the call.
+ *   tables[B][P] (P = M(M-1)/2, row-major i<j), lengths[B] (host: samples per frame, td = (k_sel - (L-1)) / fs),
+ *   mics[M][3] (host), calib[M] (host, seconds, or NULL), weights[B][P] (host; PAL_SOLVE_W_ARRAY only),
+ *   extra_starts[B][n_extra][3] (host, or NULL when n_extra = 0), out[B] (host).
+ * pal_solve_positions_dev takes the tables in HBM (e.g. straight from pal_gcc_phat_all_pairs_dev) and, because its result is
+ * a host array, returns when the positions are there.  2 <= M <= 256, 0 <= grid <= 16 with at least one start beside the
+ * centre (grid >= 1 or n_extra >= 1), fs > 0, c > 0, buffer >= 0, max_iter >= 1 (0 = the default 200): PAL_ERR_INVALID otherwise. */
+#define PAL_SOLVE_W_ONES 0   /* w = 1                                                                  */
+#define PAL_SOLVE_W_SNR 1    /* w = snr / mean(snr) of the records, as compute_weights (NumPy's mean)  */
+#define PAL_SOLVE_W_ARRAY 2  /* w = the caller's weights[B][P]                                          */
+#define PAL_SOLVE_CONVERGED 1    /* the winning start ended inside a stop rule                          */
+#define PAL_SOLVE_HIT_CAP 2      /* no start did: the record holds the lowest cost reached at max_iter  */
+#define PAL_SOLVE_BAD_WEIGHTS 4  /* a weight is not finite (an infinite SNR, utils.py:248-249): frame not solved, position NaN */
+#define PAL_SOLVE_ON_FACE 8      /* a coordinate of the position lies on a face of the box              */
+typedef struct pal_solve_params {
+  double fs;            /* sampling rate                                                      */
+  double c;             /* speed of sound                                                     */
+  double buffer;        /* dynamic_bounds_extended's buffer (main.py:246 passes 5.0)          */
+  int32_t grid;         /* cells per axis of the start grid (4: 65 starts)                    */
+  int32_t max_iter;     /* trial points per start; 0 = 200                                    */
+  int32_t weight_mode;  /* PAL_SOLVE_W_*                                                      */
+  int32_t n_extra;      /* caller starts per frame                                            */
+} pal_solve_params;
+typedef struct pal_position_record {   /* 96 bytes */
+  double position[3];
+  double cost;          /* sum(r^2) / 2 at the position                                       */
+  double lower[3];      /* the box                                                            */
+  double upper[3];
+  int32_t start;        /* index of the winning start (-1: none)                              */
+  int32_t iterations;   /* trial points it took                                               */
+  int32_t converged_starts;
+  int32_t status;       /* PAL_SOLVE_* bits                                                   */
+} pal_position_record;
+int pal_solve_positions_dev(pal_handle h, const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics,
+                            const double* calib, const double* weights, const double* extra_starts, const pal_solve_params* prm,
+                            pal_position_record* out);
+int pal_solve_positions(pal_handle h, const pal_pair_record* tables, int B, int M, const int32_t* lengths, const double* mics,
+                        const double* calib, const double* weights, const double* extra_starts, const pal_solve_params* prm,
+                        pal_position_record* out);
+
 /* single-pair signatures: phat_correlation(sig1, sig2) (utils.py:108) -> corr[n1+n2-1] */
 int pal_phat_correlation(pal_handle h, const double* sig1, int n1, const double* sig2, int n2, double* corr);
 /* get_time_delays_phat (utils.py:121): corr[n1+n2-1] (may be NULL), k_out[num_peaks] array indices */

@@ -24,6 +24,11 @@ class PhatParams(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class SolveParams(C.Structure):
+    _fields_ = [("fs", C.c_double), ("c", C.c_double), ("buffer", C.c_double), ("grid", C.c_int32), ("max_iter", C.c_int32),
+                ("weight_mode", C.c_int32), ("n_extra", C.c_int32)]
+
+
 # one row of the TDOA table (pal_pair_record, 48 bytes)
 RECORD = np.dtype([("k_sel", "<i4"), ("branch", "<i4"), ("k_argmax", "<i4"), ("n_sel", "<i4"),
                    ("cmax", "<f8"), ("cmin", "<f8"), ("snr", "<f8"), ("sel_height", "<f8")])
@@ -68,6 +73,10 @@ SIGNATURES = {
                                       C.c_uint64, C.c_void_p]),
     "pal_bootstrap_peaks_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_uint64, C.c_void_p]),
+    "pal_solve_positions_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(SolveParams), C.c_void_p]),
+    "pal_solve_positions": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(SolveParams), C.c_void_p]),
     "pal_phat_correlation": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "pal_get_time_delays_phat": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(PhatParams), C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

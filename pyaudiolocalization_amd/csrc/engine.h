@@ -94,7 +94,8 @@ enum Ws : int {
   kWsZeroRows = 14,    // per row of a call: a microphone of the pair is silent (k_pair_zero)
   kWsFin0 = 16, kWsFin1 = 17, kWsFin2 = 18,             // the finishing column pass (pfa_cols_fin.h, fin_scratch.h) per stream slot, see fin_scratch_slot
   kWsFlags = 19, kWsFlagQuads = 20, kWsFlagTable = 21,  // its flagged pairs: [flags | list | count], their packed transforms, their repaired records
-  kWsBlockTable = 23,  // (caller) records in blocked pair order (all_pairs_dev, large arrays); 22 is free
+  kWsSolve = 22,       // the position solve (solve.hip): uploaded small inputs, (b, w) per pair, starts, per-start results, records
+  kWsBlockTable = 23,  // (caller) records in blocked pair order (all_pairs_dev, large arrays)
   kWsCount = 24
 };
 constexpr Ws peak_scratch_slot(int slot) { return slot == 0 ? kWsPeaks0 : (slot == 1 ? kWsPeaks1 : kWsPeaks2); }
@@ -213,6 +214,11 @@ struct Engine {
   int bootstrap_round(const Plan& pl, int L) const;   // shuffled rows per round
   int bootstrap_peaks_dev(const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P, int32_t S, int32_t mode, int32_t block_size,
                           uint64_t seed, double* d_peaks);
+  // solve.hip: TDOA tables -> positions (d_tables in HBM, every other argument a host array); returns with `out` filled
+  int solve_positions_dev(const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics, const double* calib,
+                          const double* weights, const double* extra_starts, const pal_solve_params* prm, pal_position_record* out);
+  int32_t* solve_idx = nullptr;    // device table pair -> i | j << 16 of the last microphone count
+  int solve_idx_M = 0;
   int peaks(const double* corr, size_t stride, int rows, int n, int n2, const pal_phat_params& prm,
             pal_pair_record* table, int32_t* ksel_multi, int slot);
   // the same in pieces, for the column pass that produces the streaming statistics itself (pfa_cols_stats.h):

@@ -347,6 +347,7 @@ void pal_destroy(pal_handle h) {
   if (e->quads) hipFree(e->quads);
   if (e->quads_blk) hipFree(e->quads_blk);
   if (e->perm_blk) hipFree(e->perm_blk);
+  if (e->solve_idx) hipFree(e->solve_idx);
   for (hipEvent_t ev : e->ev_pool) hipEventDestroy(ev);
   hipStreamDestroy(e->stream2);
   hipStreamDestroy(e->stream3);
@@ -503,6 +504,27 @@ int pal_bootstrap_peaks(pal_handle h, const double* rows, int R, int L, const in
                                  seed, static_cast<double*>(dk)));
   PAL_TRY(e->check(hipMemcpyAsync(peaks, dk, pbytes, hipMemcpyDeviceToHost, e->stream), "peaks download"));
   return pal_synchronize(h);
+}
+
+int pal_solve_positions_dev(pal_handle h, const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics,
+                            const double* calib, const double* weights, const double* extra_starts, const pal_solve_params* prm,
+                            pal_position_record* out) {
+  ENGINE(h);
+  return e->solve_positions_dev(d_tables, B, M, lengths, mics, calib, weights, extra_starts, prm, out);
+}
+
+int pal_solve_positions(pal_handle h, const pal_pair_record* tables, int B, int M, const int32_t* lengths, const double* mics,
+                        const double* calib, const double* weights, const double* extra_starts, const pal_solve_params* prm,
+                        pal_position_record* out) {
+  ENGINE(h);
+  if (!tables) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  if (B < 1) return e->fail(PAL_ERR_INVALID, "need B >= 1");
+  if (M < 2) return e->fail(PAL_ERR_INVALID, "need at least 2 microphones (got %d)", M);
+  const size_t bytes = size_t(B) * size_t(M) * size_t(M - 1) / 2 * sizeof(pal_pair_record);
+  void* dt = nullptr;
+  PAL_TRY(e->scratch(kWsStageTable, bytes, &dt));
+  PAL_TRY(e->check(hipMemcpyAsync(dt, tables, bytes, hipMemcpyHostToDevice, e->stream), "tables upload"));
+  return e->solve_positions_dev(static_cast<const pal_pair_record*>(dt), B, M, lengths, mics, calib, weights, extra_starts, prm, out);
 }
 
 static int single_pair(Engine* e, const double* sig1, int n1, const double* sig2, int n2, const pal_phat_params* prm,

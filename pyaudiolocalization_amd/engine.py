@@ -13,8 +13,8 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _ffi, bootstrap
-from ._ffi import RECORD, PalError, PhatParams, f64, ptr
+from . import _ffi, bootstrap, solve
+from ._ffi import RECORD, PalError, PhatParams, SolveParams, f64, ptr
 
 
 def _method_code(threshold_method: str) -> int:
@@ -202,6 +202,56 @@ class Engine:
         code = bootstrap.check_args(mode, block_size, num_bootstrap)
         self._check(self._lib.pal_bootstrap_peaks_dev(self._h, C.c_void_p(d_rows), int(r), int(length), C.c_void_p(d_pairs), int(p),
                                                       int(num_bootstrap), code, int(block_size), int(seed), C.c_void_p(d_peaks)))
+
+    # ---- position solve (main.py:233-298; algorithm: solve.py) ----------------------------------
+    def _solve_args(self, nframes, npairs, lengths, mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter, extra_starts):
+        mics = f64(mic_positions)
+        if mics.ndim != 2 or mics.shape[1] != 3:
+            raise ValueError("mic_positions must be [M][3]")
+        m = mics.shape[0]
+        if m >= 2 and npairs != m * (m - 1) // 2:
+            raise ValueError(f"a table of {m} microphones has {m * (m - 1) // 2} rows per frame, got {npairs}")
+        ln = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.int32), (nframes,)))
+        cal = None if calib_delays is None else f64(calib_delays, (m,))
+        wt = None
+        if isinstance(weights, str):
+            if weights not in ("ones", "snr"):
+                raise ValueError("weights: 'ones', 'snr' or an array of [B][P] weights")
+            mode = solve.WEIGHTS[weights]
+        else:
+            mode = solve.WEIGHTS["array"]
+            wt = f64(weights).reshape(nframes, npairs)
+        ex = None if extra_starts is None else f64(extra_starts).reshape(nframes, -1, 3)
+        prm = SolveParams(float(fs), float(c), float(buffer), int(grid), int(max_iter), mode, 0 if ex is None else ex.shape[1])
+        return m, ln, mics, cal, wt, ex, prm
+
+    def solve_positions(self, tables, lengths, mic_positions, fs, c, calib_delays=None, weights="ones", buffer=5.0, grid=solve.GRID,
+                        max_iter=solve.MAX_ITER, extra_starts=None) -> np.ndarray:
+        """tables[B][P] (or [P]) of _ffi.RECORD, lengths[B] (or one length) -> records[B] of solve.POSITION.  ``weights``: 'ones',
+        'snr' (snr / mean(snr) of the records, as compute_weights) or an array [B][P]; ``extra_starts`` [B][n][3]."""
+        tab = np.ascontiguousarray(tables, dtype=RECORD)
+        if tab.ndim == 1:
+            tab = tab[None]
+        if tab.ndim != 2:
+            raise ValueError("tables must be [P] or [B][P]")
+        b, p = tab.shape
+        m, ln, mics, cal, wt, ex, prm = self._solve_args(b, p, lengths, mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter,
+                                                         extra_starts)
+        out = np.zeros(b, dtype=solve.POSITION)
+        self._check(self._lib.pal_solve_positions(self._h, tab.ctypes.data, b, m, ln.ctypes.data, mics.ctypes.data, ptr(cal), ptr(wt), ptr(ex),
+                                                  C.byref(prm), out.ctypes.data))
+        return out
+
+    def solve_positions_dev(self, d_tables: int, b: int, lengths, mic_positions, fs, c, calib_delays=None, weights="ones", buffer=5.0,
+                            grid=solve.GRID, max_iter=solve.MAX_ITER, extra_starts=None) -> np.ndarray:
+        """The same with the tables[B][P] in HBM (e.g. where gcc_phat_all_pairs_dev wrote them); returns when the records are on the host."""
+        m = np.asarray(mic_positions).shape[0]
+        m, ln, mics, cal, wt, ex, prm = self._solve_args(int(b), m * (m - 1) // 2, lengths, mic_positions, fs, c, calib_delays, weights, buffer,
+                                                         grid, max_iter, extra_starts)
+        out = np.zeros(int(b), dtype=solve.POSITION)
+        self._check(self._lib.pal_solve_positions_dev(self._h, C.c_void_p(d_tables), int(b), m, ln.ctypes.data, mics.ctypes.data, ptr(cal), ptr(wt),
+                                                      ptr(ex), C.byref(prm), out.ctypes.data))
+        return out
 
     def phat_correlation(self, sig1, sig2) -> np.ndarray:
         a, b = f64(sig1), f64(sig2)

@@ -3,8 +3,9 @@
 
 What changed underneath: the per-(mic, path) fractional-delay loop (main.py:104-118) is one batched
 HIP launch group, and the i<j pair loop around get_time_delays_phat (main.py:202-228) is one call
-that returns the whole TDOA table.  The 3-unknown position solve stays on the host with the same
-SciPy / scikit-learn calls as the reference (out of GPU scope).
+that returns the whole TDOA table.  The 3-unknown position solve runs on the host with the same
+SciPy / scikit-learn calls as the reference by default; ``localization["solver"] = "device"`` and
+``solve_positions_device`` take the batched device solve instead (solve.py).
 """
 from __future__ import annotations
 
@@ -138,6 +139,48 @@ def solve_position(mic_positions, mic_pairs, td_diffs, c, weights=None, clusteri
     return np.array(de.x) if de.success else np.array(guesses[0])
 
 
+def host_position(table, length, mic_positions, fs, c, calib_delays, weights, clustering=("kmeans", 0.001, 2)) -> np.ndarray:
+    """One frame through the host tail (solve_position) from its record table."""
+    m = len(mic_positions)
+    pairs = pair_list(m)
+    td = (table["k_sel"].astype(np.int64) - (int(length) - 1)) / fs
+    if calib_delays is not None:
+        cal = np.asarray(calib_delays, dtype=float)
+        td = td - (cal[pairs[:, 1]] - cal[pairs[:, 0]])
+    mic_pairs = [(int(i), int(j)) for i, j in pairs]
+    if isinstance(weights, str):
+        w = np.ones(len(mic_pairs)) if weights == "ones" else compute_weights({p: {"snr": float(s)} for p, s in zip(mic_pairs, table["snr"])},
+                                                                             mic_pairs)
+    else:
+        w = np.asarray(weights, dtype=float)
+    return solve_position(mic_positions, mic_pairs, list(td), c, w, *clustering)
+
+
+def solve_positions_device(tables, lengths, mic_positions, fs, c, calib_delays=None, weights=None, buffer=5.0, grid=4, max_iter=200,
+                           extra_starts=None, engine=None, return_records=False, clustering=("kmeans", 0.001, 2)):
+    """TDOA tables[B][P] (or [P]) -> positions[B][3] by the batched device solve (Engine.solve_positions; algorithm: solve.py).
+    ``weights``: None / 'ones', 'snr' (the records' SNR as compute_weights weighs it) or an array [B][P].  A frame the device does
+    not solve - a weight that is not finite (an infinite SNR), or no start that ended inside a stop rule - goes through the host
+    tail (solve_position) instead, as the reference would have solved it.  ``return_records``: also the solve.POSITION records."""
+    from . import solve as S
+    eng = engine or default_engine()
+    tab = np.ascontiguousarray(tables, dtype=_ffi.RECORD)
+    one = tab.ndim == 1
+    if one:
+        tab = tab[None]
+    w = "ones" if weights is None else weights
+    ln = np.broadcast_to(np.asarray(lengths, dtype=np.int64), (tab.shape[0],))
+    rec = eng.solve_positions(tab, ln, mic_positions, fs, c, calib_delays, w, buffer, grid, max_iter, extra_starts)
+    pos = rec["position"].copy()
+    for f in np.flatnonzero((rec["status"] & S.ST_CONVERGED) == 0):
+        log.warning("frame %d: the device solve has no converged start (status %d), using the host solve", f, int(rec["status"][f]))
+        wf = w if isinstance(w, str) else np.asarray(w, dtype=float).reshape(tab.shape[0], -1)[f]
+        pos[f] = host_position(tab[f], ln[f], np.asarray(mic_positions), fs, c, calib_delays, wf, clustering)
+    if one:
+        pos, rec = pos[0], rec[0]
+    return (pos, rec) if return_records else pos
+
+
 def localize_sound_source(config, calibration_data=None, audio_files=None, use_simulation=True, show_plots=True):
     fs = config["fs"]
     duration = config["duration"]
@@ -158,6 +201,9 @@ def localize_sound_source(config, calibration_data=None, audio_files=None, use_s
     max_expected_delay = loc.get("max_expected_delay", None)
     bootstrap_rng = loc.get("bootstrap_rng", "numpy")        # "device": counter-based shuffles, all pairs in one call
     bootstrap_seed = loc.get("bootstrap_seed", 0)
+    solver = loc.get("solver", "host")                       # "device": the batched Levenberg-Marquardt solve (solve.py)
+    if solver not in ("host", "device"):
+        raise ValueError("localization.solver must be 'host' or 'device'")
 
     calib_delays = None
     if calibration_data is not None:                                           # main.py:147-157
@@ -227,8 +273,12 @@ def localize_sound_source(config, calibration_data=None, audio_files=None, use_s
     # ---- host tail: main.py:233-298 ---------------------------------------------------------------
     weights = compute_weights(correlation_metrics, mic_pairs) if analyze_correlation and correlation_metrics \
         else np.ones(len(mic_pairs))
-    position = solve_position(mic_positions, mic_pairs, td_diffs, c, weights, clustering_method, clustering_eps,
-                              clustering_min_samples)
+    if solver == "device":
+        position = solve_positions_device(table, n2, mic_positions, fs, c, calib_delays, weights,
+                                          clustering=(clustering_method, clustering_eps, clustering_min_samples))
+    else:
+        position = solve_position(mic_positions, mic_pairs, td_diffs, c, weights, clustering_method, clustering_eps,
+                                  clustering_min_samples)
     log.info("estimated source: (%.3f, %.3f, %.3f) m", *position)
 
     # ---- plots: main.py:300-319 (files are written when show_plots is False) ------------

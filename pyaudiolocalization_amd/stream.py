@@ -16,6 +16,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import solve
 from ._ffi import RECORD
 from .engine import Engine, default_engine, make_params
 from .signal_processing import _filter_design
@@ -26,6 +27,30 @@ def tdoa_stream(bases: Sequence[np.ndarray], delays: Sequence[np.ndarray], gains
                 totals: Sequence[int], trim_len: int, filter_method: str = "butterworth",
                 max_expected_delay: Optional[float] = None, engine: Optional[Engine] = None,
                 frames_per_batch: int = 128, timings: Optional[Dict[str, float]] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """bases[F][nbase], delays / gains[F][M][K], totals[F] (main.py:102) -> (tables[F][P], lengths[F]); see _chain."""
+    tables, lengths, _ = _chain(bases, delays, gains, fs, totals, trim_len, filter_method, max_expected_delay, engine, frames_per_batch,
+                                timings, None)
+    return tables, lengths
+
+
+def position_stream(bases: Sequence[np.ndarray], delays: Sequence[np.ndarray], gains: Sequence[np.ndarray], fs: float,
+                    totals: Sequence[int], trim_len: int, mic_positions, c: float, filter_method: str = "butterworth",
+                    max_expected_delay: Optional[float] = None, engine: Optional[Engine] = None, frames_per_batch: int = 128,
+                    timings: Optional[Dict[str, float]] = None, calib_delays=None, weights: str = "ones", buffer: float = 5.0,
+                    grid: int = solve.GRID, max_iter: int = solve.MAX_ITER) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The chain of tdoa_stream with the position solve (solve.py) run on the table buffer while it is still in HBM:
+    -> (positions[F] of solve.POSITION records, tables[F][P], lengths[F]).  Tables and lengths are tdoa_stream's; the positions are
+    what Engine.solve_positions returns for those tables (``weights``: 'ones' or 'snr').  A frame without the converged bit in
+    ``positions["status"]`` is the caller's to hand to main.solve_positions_device / solve_position."""
+    if weights not in ("ones", "snr"):
+        raise ValueError("weights: 'ones' or 'snr'")
+    args = dict(mic_positions=mic_positions, fs=fs, c=c, calib_delays=calib_delays, weights=weights, buffer=buffer, grid=grid, max_iter=max_iter)
+    tables, lengths, positions = _chain(bases, delays, gains, fs, totals, trim_len, filter_method, max_expected_delay, engine,
+                                        frames_per_batch, timings, args)
+    return positions, tables, lengths
+
+
+def _chain(bases, delays, gains, fs, totals, trim_len, filter_method, max_expected_delay, engine, frames_per_batch, timings, solve_args):
     """bases[F][nbase], delays / gains[F][M][K], totals[F] (main.py:102) -> (tables[F][P], lengths[F]).
 
     ``trim_len`` = int(duration * fs) (main.py:119-120).  ``frames_per_batch`` bounds the HBM held by one batch
@@ -57,6 +82,7 @@ def tdoa_stream(bases: Sequence[np.ndarray], delays: Sequence[np.ndarray], gains
         raise ValueError("Unknown filter method. Available methods: 'butterworth', 'fir', 'wiener'")
     tables = np.zeros((nf, npairs), dtype=RECORD)
     lengths = np.zeros(nf, dtype=np.int64)
+    positions = np.zeros(nf, dtype=solve.POSITION) if solve_args is not None else None
 
     def out_len_of(total: int) -> int:
         return trim_len if 0 < trim_len < total else total
@@ -143,6 +169,11 @@ def tdoa_stream(bases: Sequence[np.ndarray], delays: Sequence[np.ndarray], gains
                         row0 += len(local)
                     eng.synchronize()
                     lap("pairs")
+                    if solve_args is not None:                                                                 # main.py:233-298
+                        order = [q for local in by_len.values() for q in local]
+                        lens_b = [length for length, local in by_len.items() for _ in local]
+                        positions[[group[q] for q in order]] = eng.solve_positions_dev(d_tab, b, lens_b, **solve_args)
+                        lap("solve")
                     got = np.zeros((b, npairs), dtype=RECORD)
                     eng.download(got, d_tab)
                     row0 = 0
@@ -156,4 +187,4 @@ def tdoa_stream(bases: Sequence[np.ndarray], delays: Sequence[np.ndarray], gains
                     eng.free(d_al); eng.free(d_flt); eng.free(d_tab)
             finally:
                 eng.free(d_sim)
-    return tables, lengths
+    return tables, lengths, positions

@@ -35,7 +35,9 @@ struct Partial {                         // one segment's share of the streaming
   double plat;                           // fused column pass only: highest sample with an equal neighbour (-inf: none)
   double pfloor;                         // fused column pass only: samples of this segment below it had no peak test
   long long below;
-  int imax, imin, mb, pad;
+  int imax;                              // np.argmax inside the segment (-1: no sample recorded)
+  int has_min;                           // 1: vmin holds the segment's minimum
+  int mb, pad;                           // position of hb (-1: no local maximum)
 };
 
 // Fused column pass: a column block's histogram of |x| around ITS median, 128 logarithmic bins per octave (seven mantissa
@@ -71,10 +73,10 @@ struct PeakArgs {
   int n, n2;
   double fs, mult, med;   // med: NaN = no window
   int method, dist, num_peaks, snr_w;   // method: 0 median, 1 adaptive, < 0 metrics only
-  int splits, tiles_per_seg;             // segments per row, tiles per segment
-  int local_pivots;                      // 1: fused column pass - no RowPre, no bracket lists: every segment brought a histogram
-                                         //    window (BlockHist) and its own bound for untested samples (Partial.pfloor)
-  BlockHist* bh;                         // [rows][splits] (local_pivots only)
+  int splits, tiles_per_seg;             // segments per row; tiles per segment of the stream launch, or 0: the segments are column blocks
+                                         // of the fused column pass (k_peak_finish<true>) - no RowPre, no bracket lists: every segment
+                                         // brought a histogram window (BlockHist) and its own bound for untested samples (Partial.pfloor)
+  BlockHist* bh;                         // [rows][splits] (fused column pass only)
   int edge_n2;                           // > 0: segments are column blocks of the prime-factor grid (row length edge_n2; block q holds the
                                          //      columns [q n2 / splits, (q + 1) n2 / splits));
                                          //      the finish launch tests the samples of columns 0 and edge_n2 - 1 itself

@@ -305,7 +305,7 @@ __global__ __launch_bounds__(64 * NW) void k_pfa_cols_stats(const cd* __restrict
     Partial pt;
     pt.vmax = pt.hb = pt.plat = -INFINITY;
     pt.vmin = INFINITY;
-    pt.imax = pt.imin = pt.mb = -1;
+    pt.imax = pt.mb = -1;
     pt.s1 = pt.s2 = pt.a1 = pt.a2 = 0;
     pt.below = 0;
     pt.pad = 0;
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(64 * NW) void k_pfa_cols_stats(const cd* __restrict
       pt.plat = fmax(pt.plat, x.plat);
     }
     pt.a2 = pt.s2;                                              // sum |x|^2 = sum x^2 (both shifts are zero on this path)
-    pt.imin = 0;                                                // (the finish launch only asks whether the segment has a minimum)
+    pt.has_min = 1;
     double bmax = wmax[0][r];
     for (int w = 1; w < NW; ++w) bmax = fmax(bmax, wmax[w][r]);
     pt.pfloor = bmax > 0 ? 0.8 * bmax : -INFINITY;

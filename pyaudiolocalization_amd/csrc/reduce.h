@@ -16,17 +16,6 @@ template <int NW = 4> __device__ inline double block_sum(double v, double* rd, i
   return r;
 }
 
-template <int NW = 4> __device__ inline long long block_sum_ll(long long v, long long* rl, int tid) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();
-  if ((tid & 63) == 0) rl[tid >> 6] = v;
-  __syncthreads();
-  long long r = 0;
-#pragma unroll
-  for (int k = 0; k < NW; ++k) r += rl[k];
-  return r;
-}
-
 template <int NW = 4> __device__ inline double block_max(double v, double* rd, int tid) {
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
   __syncthreads();

@@ -208,6 +208,11 @@ int pal_get_time_delays_phat(pal_handle h, const double* sig1, int n1, const dou
                              const pal_phat_params* prm, int32_t* k_out, pal_pair_record* rec, double* corr);
 /* compute_snr / compute_peak_to_peak_ratio / max on an existing correlation row (utils.py:228-250) */
 int pal_corr_metrics(pal_handle h, const double* corr, int n, pal_pair_record* rec);
+/* get_time_delays_phat's selection (utils.py:144-179) and the record's metrics on existing rows: corr[R][n] (host),
+ * n2 as in the lag mapping k - (n2 - 1), table[R], k_out[R][num_peaks] (may be NULL; -1 past n_sel).  A non-finite
+ * sample is PAL_ERR_INVALID, found on the host before anything is launched. */
+int pal_select_peaks(pal_handle h, const double* corr, int R, int n, int n2, const pal_phat_params* prm,
+                     pal_pair_record* table, int32_t* k_out);
 
 /* ---- hot path B: image-source multipath simulation ------------------------------------
  * generate_image_sources_iterative (utils.py:67-106): host C++, discovery order preserved.

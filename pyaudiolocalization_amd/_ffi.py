@@ -81,6 +81,7 @@ SIGNATURES = {
     "pal_get_time_delays_phat": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(PhatParams), C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
     "pal_corr_metrics": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
+    "pal_select_peaks": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(PhatParams), C.c_void_p, C.c_void_p]),
     "pal_image_sources": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_double, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                     C.POINTER(C.c_int)]),

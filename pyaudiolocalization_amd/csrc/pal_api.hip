@@ -590,6 +590,31 @@ int pal_corr_metrics(pal_handle h, const double* corr, int n, pal_pair_record* r
   return pal_synchronize(h);
 }
 
+int pal_select_peaks(pal_handle h, const double* corr, int R, int n, int n2, const pal_phat_params* prm,
+                     pal_pair_record* table, int32_t* k_out) {
+  ENGINE(h);
+  PAL_TRY(validate(e, prm));
+  if (!corr || !table) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  if (R < 1 || n < 1 || n2 < 1 || n2 > n) return e->fail(PAL_ERR_INVALID, "need R >= 1, n >= 1, 1 <= n2 <= n (got %d, %d, %d)", R, n, n2);
+  if (int64_t(R) * ((n + 2047) / 2048) > INT32_MAX) return e->fail(PAL_ERR_UNSUPPORTED, "too many rows");   // (one workgroup per tile at most)
+  const size_t count = size_t(R) * size_t(n);
+  for (size_t i = 0; i < count; ++i)                           // on the host, before any upload or launch
+    if (!std::isfinite(corr[i]))
+      return e->fail(PAL_ERR_INVALID, "non-finite sample (NaN or infinity) in correlation row %lld", (long long)(i / size_t(n)));
+  const size_t tbytes = size_t(R) * sizeof(pal_pair_record);
+  void *dc = nullptr, *dt = nullptr;
+  PAL_TRY(e->scratch(kWsStageOut, count * sizeof(double), &dc));
+  PAL_TRY(e->scratch(kWsStageTable, tbytes + size_t(R) * PAL_MAX_PEAKS * sizeof(int32_t), &dt));
+  int32_t* dk = reinterpret_cast<int32_t*>(static_cast<char*>(dt) + tbytes);
+  PAL_TRY(e->check(hipMemcpyAsync(dc, corr, count * sizeof(double), hipMemcpyHostToDevice, e->stream), "corr upload"));
+  PAL_TRY(e->peaks(static_cast<const double*>(dc), size_t(n), R, n, n2, *prm, static_cast<pal_pair_record*>(dt), dk, 0));   // slot 0: on `stream`
+  PAL_TRY(e->check(hipMemcpyAsync(table, dt, tbytes, hipMemcpyDeviceToHost, e->stream), "table download"));
+  if (k_out)
+    PAL_TRY(e->check(hipMemcpy2DAsync(k_out, size_t(prm->num_peaks) * sizeof(int32_t), dk, PAL_MAX_PEAKS * sizeof(int32_t),
+                                      size_t(prm->num_peaks) * sizeof(int32_t), size_t(R), hipMemcpyDeviceToHost, e->stream), "k download"));
+  return pal_synchronize(h);
+}
+
 int pal_plan_info(pal_handle h, int L, int32_t* n, int32_t* conv_len, int32_t* m1, int32_t* m2) {
   ENGINE(h);
   if (L < 1 || L > (1 << 20)) return e->fail(PAL_ERR_INVALID, "bad frame length");

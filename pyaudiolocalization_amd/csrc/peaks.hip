@@ -1072,10 +1072,12 @@ __device__ __forceinline__ double row_snr(const PeakArgs& a, const double* c, Sh
   w2 = wsum[1];
   const double nn = double(n - (whi_s - wlo_s));
   double o1 = r.s1 - w1, o2 = r.s2 - w2;
-  if (!(o2 >= 0.25 * r.s2)) {
+  if (!(o2 >= 0.25 * r.s2) || nn == 1.0) {
     // the window holds most of the row's energy (strongly correlated signals: a near-delta sequence), so
     // "total minus window" would cancel: sum the noise region itself in one more pass
-    // (two passes like np.std: the sample mean k0 may sit 1e3 noise sigmas away when it caught the peak)
+    // (two passes like np.std: the sample mean k0 may sit 1e3 noise sigmas away when it caught the peak).
+    // A noise region of ONE sample (n = 2, 3) goes the same way: its deviation is exactly 0 and the SNR infinite, as
+    // np.std gives it; the difference of the one-pass sums leaves a rounding residue there
     double q1 = 0, q2 = 0;
     for (int i = tid; i < n; i += kT)
       if (i < wlo_s || i >= whi_s) q1 += c[i];

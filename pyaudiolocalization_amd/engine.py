@@ -282,6 +282,22 @@ class Engine:
         self._check(self._lib.pal_corr_metrics(self._h, c.ctypes.data, c.shape[0], rec.ctypes.data))
         return rec[0]
 
+    def select_peaks(self, rows, n2, fs, num_peaks=1, threshold_method="median", threshold_multiplier=1.0,
+                     max_expected_delay=None):
+        """Existing correlation rows[R][n] (or one row) with the lag mapping k - (n2 - 1) -> (table[R], k[R][num_peaks]);
+        entries of k past a row's n_sel are -1."""
+        x = f64(rows)
+        if x.ndim == 1:
+            x = x[None]
+        if x.ndim != 2:
+            raise ValueError("rows must be [n] or [R][n]")
+        prm = make_params(fs, num_peaks, threshold_method, threshold_multiplier, max_expected_delay)
+        table = np.zeros(x.shape[0], dtype=RECORD)
+        ks = np.full((x.shape[0], max(1, int(num_peaks))), -1, dtype=np.int32)
+        self._check(self._lib.pal_select_peaks(self._h, x.ctypes.data, x.shape[0], x.shape[1], int(n2), C.byref(prm),
+                                               table.ctypes.data, ks.ctypes.data))
+        return table, ks
+
     # ---- hot path B --------------------------------------------------------------------
     def simulate_multipath(self, base, fs, total_samples, delays, gains, trim_len=0) -> np.ndarray:
         """base[B][nbase], delays/gains[B][M][K] -> out[B][M][out_len] (normalised + compressed)."""

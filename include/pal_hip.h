@@ -224,8 +224,10 @@ int pal_image_sources(const double* source, const double* planes, const int32_t*
                       double* images, int32_t* image_material, int cap, int* count);
 /* simulate_signals_with_multipath (main.py:103-123) after the path geometry is known:
  * base[B][nbase] zero-padded to total_samples, delays/gains[B][M][K] (seconds, linear gain, fp64),
- * out[B][M][out_len] with out_len = trim_len > 0 ? trim_len : total_samples; fractional_delay
- * (signal_processing.py:66-80), normalize_signal + dynamic_range_compression (:82-94) fused. */
+ * out[B][M][out_len] with out_len = trim_len if 0 < trim_len < total_samples, else total_samples (the slice
+ * [:trim_len] of main.py:119-120 never lengthens a row); fractional_delay (signal_processing.py:66-80),
+ * normalize_signal + dynamic_range_compression (:82-94) fused.  100 <= total_samples <= 2^19 and nbase <= total_samples,
+ * or the call is refused.  A microphone whose gains are all zero gives an all-zero row, as the reference's sum does. */
 int pal_simulate_multipath(pal_handle h, const double* base, int B, int nbase, double fs, int total_samples,
                            const double* delays, const double* gains, int M, int K, int trim_len, double* out);
 /* fractional_delay(signal, delay, fs) alone (signal_processing.py:66-80); rows[R][N], delay per row */

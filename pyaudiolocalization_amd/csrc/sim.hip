@@ -89,12 +89,24 @@ struct SimStorer {
 // normalize_signal / dynamic_range_compression, one workgroup per row (signal_processing.py:82-94).
 // max|compressed| is the compressed value of the row maximum (|x/max| = 1 exactly, log1p monotone),
 // so one max reduction serves both normalisations.
+// `gains` (optional, [rows][K]): a synthesised row whose path gains are all zero is zero in the reference (a sum of
+// 0 * fractional_delay), but here it is one half of a complex transform and carries its partner's rounding noise, which
+// the normalisation would blow up to full scale: such a row is written as zeros.
 __global__ __launch_bounds__(256) void k_norm_compress(const double* in, size_t istride, double* out, size_t ostride,
-                                                       int len, int normalize_only, double thr, double eps) {
+                                                       int len, int normalize_only, double thr, double eps,
+                                                       const double* gains, int K) {
   __shared__ double rd[4];
   const int tid = threadIdx.x;
   const double* x = in + size_t(blockIdx.x) * istride;
   double* y = out + size_t(blockIdx.x) * ostride;
+  if (gains) {
+    bool silent = true;
+    for (int p = 0; p < K; ++p) silent = silent && gains[size_t(blockIdx.x) * K + p] == 0;
+    if (silent) {                                            // (uniform over the workgroup)
+      for (int i = tid; i < len; i += kLanes) y[i] = 0.0;
+      return;
+    }
+  }
   double m = 0;
   for (int i = tid; i < len; i += kLanes) m = fmax(m, fabs(x[i]));
   m = block_max(m, rd, tid);
@@ -389,7 +401,7 @@ static int simulate_dev(Engine* e, const double* d_base, int bases, int nbase, d
   if (compress || normalize) {
     ProfScope ps(e, "k_norm_compress");
     k_norm_compress<<<dim3(rows), dim3(kLanes), 0, e->stream>>>(d_out, size_t(out_len), d_out, size_t(out_len), out_len,
-                                                               compress ? 0 : 1, 0.8, 1e-8);
+                                                               compress ? 0 : 1, 0.8, 1e-8, d_gains, K);
     PAL_TRY(e->check(hipGetLastError(), "k_norm_compress"));
   }
   return PAL_OK;
@@ -538,7 +550,7 @@ int pal_normalize_compress(pal_handle h, const double* rows_in, int R, int N, in
   {
     ProfScope ps(e, "k_norm_compress");
     k_norm_compress<<<dim3(R), dim3(kLanes), 0, e->stream>>>(static_cast<double*>(db), size_t(N), static_cast<double*>(db),
-                                                            size_t(N), N, normalize_only, threshold, epsilon);
+                                                            size_t(N), N, normalize_only, threshold, epsilon, nullptr, 0);
   }
   PAL_TRY(e->check(hipGetLastError(), "k_norm_compress"));
   DOWN(out, db, size_t(R) * N * sizeof(double));

@@ -378,15 +378,19 @@ class Engine:
                                                          C.c_void_p(d_delays), C.c_void_p(d_gains), int(m), int(k), int(trim_len),
                                                          C.c_void_p(d_out)))
 
+    def row_energies_dev(self, d_rows: int, r: int, n: int) -> np.ndarray:
+        """Sum of squares of every row of d_rows[r][n] (device summation order) -> energy[r] on the host."""
+        en = np.zeros(r)
+        self._check(self._lib.pal_row_energies_dev(self._h, C.c_void_p(d_rows), int(r), int(n), en.ctypes.data))
+        return en
+
     def sync_measure_dev(self, d_rows: int, b: int, m: int, n: int):
         """Per frame: reference microphone (highest energy) and the cross-correlation measurements of every row against it
         -> (ref_idx[B], kpk[B][M], win5[B][M][5], pkabs[B][M], refpk[B]) on the host (a few numbers per row)."""
         # The reference microphone is np.argmax of np.sum(sig**2) (utils.py:413-414).  The device sums in another order: where the two
         # highest energies of a frame agree to 1e-12 (mirrored geometries, equal rows) those rows come to the host and numpy
         # itself decides, so that the choice - and with it every shift, pad and length behind it - is the reference's.
-        en = np.zeros(b * m)
-        self._check(self._lib.pal_row_energies_dev(self._h, C.c_void_p(d_rows), int(b * m), int(n), en.ctypes.data))
-        en = en.reshape(b, m)
+        en = self.row_energies_dev(d_rows, b * m, n).reshape(b, m)
         ref = np.full(b, -1, dtype=np.int32)
         for f in range(b):
             if not np.all(np.isfinite(en[f])):

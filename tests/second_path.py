@@ -1,0 +1,343 @@
+"""Case builders for the second path (csrc/sim.hip): multipath synthesis and ``fractional_delay``, normalise /
+compress, the tiled ``filtfilt`` and its ragged form, ``wiener3``, the cross-correlation + peak chain behind
+``synchronize_signals_improved``, row energies and ``align_rows``.  Plain helper module like ``peak_rows.py``: it
+imports neither pytest nor the engine, every row is seeded and named, and the references that can be exact are.
+
+``FILTERS``: name -> (b, a), tap counts K = 2, 5, 4, 11, 5, 101, 4, 3 (``nb != na`` and a non-unit ``a[0]`` among
+them); ``zi(name)`` is ``scipy.signal.lfilter_zi``.  ``family(name, seed, n)`` draws one row of a family.
+``exact_xcorr`` / ``exact_shift`` / ``fsum_energy`` are references without rounding error of their own (integer
+samples, whole-sample delays, ``math.fsum``).
+
+Exact properties of the correlation inputs: ``xcorr_case`` / ``sync_case`` / ``crafted_cases`` assert for every row
+that the largest |value| of its exact correlation with the reference row is unique and exceeds the runner-up by at
+least 1 (a correlation of one sample has no runner-up).  That is a condition on the inputs, checked without a GPU:
+the seeds in ``XCORR_SEEDS`` / ``SYNC_SEED`` were drawn until every row passed (``find_seed``), and no row is left
+out of a comparison.
+"""
+from __future__ import annotations
+
+import math
+from collections import namedtuple
+from typing import Dict, List, Tuple
+
+import numpy as np
+
+from oracle import pal_oracle as O
+
+FS = 8000.0
+SENTINEL_BITS = 0x47D5A5A5DEADBEEF               # a finite double (about 1.1e+38) no kernel here produces
+SENTINEL = float(np.array([SENTINEL_BITS], dtype=np.uint64).view(np.float64)[0])
+
+FAMILIES = ("normal", "constant", "zeros", "step", "spike", "tiny", "huge", "ints")
+
+
+# ------------------------------------------------------------------------------------------------ filters
+def _filters() -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
+    from scipy.signal import butter, firwin
+    one = np.array([1.0])
+    b3, a3 = butter(3, 0.25)
+    return {
+        "butter1": butter(1, 0.3),                                        # K = 2: the shortest recurrence
+        "butter2bp": butter(2, [0.1, 0.4], btype="band"),                 # K = 5
+        "butter3": (b3, a3),                                              # K = 4
+        "butter5bp": O.butter_bandpass(FS),                               # K = 11: the register-state instantiation
+        "fir5": (firwin(5, 0.3), one),                                    # K = 5, na = 1
+        "fir101": (firwin(101, [300 / 4000.0, 3400 / 4000.0], pass_zero=False), one),   # K = 101
+        "scaled": (2.5 * b3, 2.5 * a3),                                   # K = 4, a[0] = 2.5
+        "short_b": (np.array([0.3]), np.array([1.0, -0.5, 0.2])),         # K = 3, nb = 1 < na = 3
+    }
+
+
+FILTERS = {k: (np.asarray(b, dtype=np.float64), np.asarray(a, dtype=np.float64)) for k, (b, a) in _filters().items()}
+FILTER_K = {"butter1": 2, "butter2bp": 5, "butter3": 4, "butter5bp": 11, "fir5": 5, "fir101": 101, "scaled": 4, "short_b": 3}
+assert {k: max(len(b), len(a)) for k, (b, a) in FILTERS.items()} == FILTER_K
+
+
+def taps(name: str) -> int:
+    return FILTER_K[name]
+
+
+def zi(name: str) -> np.ndarray:
+    from scipy.signal import lfilter_zi
+    return np.asarray(lfilter_zi(*FILTERS[name]), dtype=np.float64)
+
+
+def host_lengths(name: str) -> Tuple[int, ...]:
+    """the five lengths at which the oracle is pinned to scipy"""
+    k = taps(name)
+    return (3 * k + 1, 3 * k + 2, 3 * k + 63, 3 * k + 64, 6 * k + 130)
+
+
+def gpu_lengths(name: str) -> Tuple[int, ...]:
+    """one and two samples past the pad length, and the extended length N + 6 K on 64 m - 1, 64 m, 64 m + 1 (m >= 2 the
+    smallest for which all three are longer than the pad length)"""
+    k = taps(name)
+    m = 2
+    while 64 * m - 1 - 6 * k < 3 * k + 1:
+        m += 1
+    base = 64 * m - 6 * k
+    return (3 * k + 1, 3 * k + 2, base - 1, base, base + 1)
+
+
+def filter_rows(name: str) -> Tuple[int, ...]:
+    return (1, 3) if name == "fir101" else (1, 63, 64, 65, 130)
+
+
+# ------------------------------------------------------------------------------------------------ row families
+def family(name: str, seed, n: int) -> np.ndarray:
+    rng = np.random.default_rng(seed)
+    if name == "normal":
+        x = rng.standard_normal(n)
+    elif name == "constant":
+        x = np.full(n, float(rng.uniform(0.5, 2.0)) * (-1.0 if rng.integers(0, 2) else 1.0))
+    elif name == "zeros":
+        x = np.zeros(n)
+    elif name == "step":
+        x = np.zeros(n)
+        x[n // 2:] = float(rng.uniform(0.5, 2.0))
+    elif name == "spike":
+        x = np.zeros(n)
+        x[int(rng.integers(0, n))] = 1e6
+    elif name == "tiny":
+        x = rng.standard_normal(n) * 1e-160
+    elif name == "huge":
+        x = rng.standard_normal(n) * 1e150
+    elif name == "ints":
+        x = rng.integers(-8, 9, n).astype(np.float64)
+    else:
+        raise KeyError(name)
+    return np.ascontiguousarray(x, dtype=np.float64)
+
+
+# ------------------------------------------------------------------------------------------------ exact references
+def exact_xcorr(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """np.correlate(a, b, 'full') for integer-valued rows: every product and partial sum is an integer below 2^53"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    assert np.array_equal(a, np.rint(a)) and np.array_equal(b, np.rint(b))
+    assert float(np.sum(np.abs(a))) * float(np.max(np.abs(b), initial=0.0)) < 2.0 ** 53
+    return np.correlate(a, b, "full")
+
+
+def exact_shift(x: np.ndarray, k: int) -> np.ndarray:
+    """fractional_delay(x, k / fs, fs) for a whole-sample delay: the row moved by k samples (zeros move in: the transform
+    has 2 N points), times the fade window"""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.zeros_like(x)
+    y[k:] = x[:x.shape[0] - k]
+    return y * O.fade_window(x.shape[0])
+
+
+def fsum_energy(row) -> float:
+    return math.fsum(float(v) * float(v) for v in row)
+
+
+# ------------------------------------------------------------------------------------------------ correlation inputs
+XcorrCase = namedtuple("XcorrCase", "name rows refs exact")       # exact[ref][r]: the exact 2 N - 1 sequence of row r against row ref
+
+XCORR_N = (1, 2, 3, 5, 64, 700, 1025)
+XCORR_R = (1, 2, 7)
+
+
+def ref_choices(r: int) -> Tuple[int, ...]:
+    return tuple(sorted({0, r // 2, r - 1}))
+
+
+def peak_margin(seq: np.ndarray) -> float:
+    """largest |value| minus the runner-up (inf for a single sample)"""
+    mag = np.sort(np.abs(np.asarray(seq, dtype=np.float64)))
+    return float("inf") if mag.size == 1 else float(mag[-1] - mag[-2])
+
+
+def _exact_table(rows: np.ndarray, refs) -> Dict[int, List[np.ndarray]]:
+    return {ref: [exact_xcorr(row, rows[ref]) for row in rows] for ref in refs}
+
+
+def _unique_peaks(exact: Dict[int, List[np.ndarray]]) -> bool:
+    return all(peak_margin(seq) >= 1.0 for seqs in exact.values() for seq in seqs)
+
+
+def _ints_rows(seed: int, r: int, n: int) -> np.ndarray:
+    return np.random.default_rng([2024, seed, r, n]).integers(-8, 9, (r, n)).astype(np.float64)
+
+
+def find_seed(make, refs_of) -> int:
+    """first seed whose rows all have a unique correlation peak with margin 1 (how the tables below were drawn)"""
+    seed = 0
+    while True:
+        rows = make(seed)
+        if _unique_peaks(_exact_table(rows, refs_of(rows))):
+            return seed
+        seed += 1
+
+
+# (N, R) -> seed, drawn with find_seed(lambda s: _ints_rows(s, R, N), lambda rows: ref_choices(R))
+XCORR_SEEDS = {
+    (1, 1): 0, (1, 2): 0, (1, 7): 0,
+    (2, 1): 0, (2, 2): 0, (2, 7): 0,
+    (3, 1): 0, (3, 2): 0, (3, 7): 3,
+    (5, 1): 0, (5, 2): 0, (5, 7): 0,
+    (64, 1): 0, (64, 2): 0, (64, 7): 1,
+    (700, 1): 0, (700, 2): 0, (700, 7): 0,
+    (1025, 1): 0, (1025, 2): 0, (1025, 7): 0,
+}
+
+_XCORR: Dict[Tuple[int, int], XcorrCase] = {}
+
+
+def xcorr_case(n: int, r: int) -> XcorrCase:
+    if (n, r) not in _XCORR:
+        rows = _ints_rows(XCORR_SEEDS[(n, r)], r, n)
+        refs = ref_choices(r)
+        exact = _exact_table(rows, refs)
+        for ref in refs:
+            for q, seq in enumerate(exact[ref]):
+                assert peak_margin(seq) >= 1.0, "ints N=%d R=%d: row %d against row %d has no unique peak" % (n, r, q, ref)
+        rows.setflags(write=False)
+        _XCORR[(n, r)] = XcorrCase("ints/n%d_r%d" % (n, r), rows, refs, exact)
+    return _XCORR[(n, r)]
+
+
+SYNC_B, SYNC_M, SYNC_N = 3, 5, 700
+SYNC_LOUD = (0, 2, 4)                             # the louder row of frame f
+SYNC_SEED = 0                                     # find_seed(_sync_rows, ...) over the three frames
+
+
+def _sync_rows(seed: int) -> np.ndarray:
+    rows = np.random.default_rng([2025, seed]).integers(-8, 9, (SYNC_B, SYNC_M, SYNC_N)).astype(np.float64)
+    for f, q in enumerate(SYNC_LOUD):
+        rows[f, q] *= 3.0
+    return rows
+
+
+def sync_case():
+    """frames[B][M][N] of integer rows, one three times louder per frame; -> (frames, ref_idx[B] as numpy's, exact[f][r])"""
+    frames = _sync_rows(SYNC_SEED)
+    refs = [int(np.argmax([np.sum(row ** 2) for row in fr])) for fr in frames]
+    assert refs == list(SYNC_LOUD)
+    exact = []
+    for f, fr in enumerate(frames):
+        table = _exact_table(fr, (refs[f],))[refs[f]]
+        for q, seq in enumerate(table):
+            assert peak_margin(seq) >= 1.0, "sync frame %d row %d has no unique peak" % (f, q)
+        exact.append(table)
+    return frames, refs, exact
+
+
+def _impulses(n: int, *pairs) -> np.ndarray:
+    x = np.zeros(n)
+    for at, amp in pairs:
+        x[at] += amp
+    return x
+
+
+def crafted_cases(n: int) -> List[XcorrCase]:
+    """Impulse rows whose exact peak sits at index 0, 1, 2, N - 1 (the reference itself), 2N - 4, 2N - 3 and 2N - 2 of the
+    2N - 1 sequence, and a row whose largest-magnitude value is negative.  The reference row carries the highest energy
+    (amplitude 4 against 3), so synchronize_signals picks it; rows peak at 12 of the reference's 16 and take the spline
+    where the five-sample window fits.  Two batches: a reference impulse at N - 1 reaches the low indices, one at 0 the
+    high ones.  ``name`` carries the expected peak index of every row."""
+    assert n >= 5
+    out = []
+    low = np.array([_impulses(n, (0, 3.0)), _impulses(n, (1, 3.0)), _impulses(n, (2, 3.0)),
+                    _impulses(n, (n // 2, -3.0), (n - 1, 1.0)), _impulses(n, (n - 1, 4.0))])
+    want_low = (0, 1, 2, n // 2, n - 1)
+    high = np.array([_impulses(n, (0, 4.0)), _impulses(n, (n - 3, 3.0)), _impulses(n, (n - 2, 3.0)), _impulses(n, (n - 1, 3.0)),
+                     _impulses(n, (n // 2, -3.0), (0, 1.0))])
+    want_high = (n - 1, 2 * n - 4, 2 * n - 3, 2 * n - 2, n - 1 + n // 2)
+    for tag, rows, ref, want in (("low", low, 4, want_low), ("high", high, 0, want_high)):
+        exact = _exact_table(rows, (ref,))
+        for q, seq in enumerate(exact[ref]):
+            assert peak_margin(seq) >= 1.0, "crafted %s N=%d row %d" % (tag, n, q)
+            assert int(np.argmax(np.abs(seq))) == want[q], (tag, n, q)
+        assert int(np.argmax([np.sum(row ** 2) for row in rows])) == ref
+        neg = 3 if tag == "low" else 4
+        assert exact[ref][neg][want[neg]] < 0                      # the largest-magnitude value of that row is negative
+        rows.setflags(write=False)
+        out.append(XcorrCase("crafted/%s_n%d" % (tag, n), rows, (ref,), exact))
+    return out
+
+
+def all_xcorr_inputs():
+    """runs every uniqueness assertion of the module (the host suite calls this)"""
+    count = 0
+    for n in XCORR_N:
+        for r in XCORR_R:
+            c = xcorr_case(n, r)
+            count += sum(len(v) for v in c.exact.values())
+    for n in (5, 64):
+        for c in crafted_cases(n):
+            count += sum(len(v) for v in c.exact.values())
+    _, _, exact = sync_case()
+    count += sum(len(v) for v in exact)
+    return count
+
+
+# ------------------------------------------------------------------------------------------------ filter inputs and answers
+_FILT_ROWS: Dict[Tuple[str, int], np.ndarray] = {}
+_FILT_WANT: Dict[Tuple[str, int, int], np.ndarray] = {}
+CONSTANT_ROW, STEP_ROW = 1000, 1001               # pool indices of the two special rows
+
+
+def filter_pool_row(name: str, n: int, idx: int) -> np.ndarray:
+    """row idx of the pool of (filter, N): 'normal' rows, and one 'constant' and one 'step' row behind them"""
+    if idx == CONSTANT_ROW:
+        return family("constant", [31, taps(name), n], n)
+    if idx == STEP_ROW:
+        return family("step", [32, taps(name), n], n)
+    key = (name, n)
+    if key not in _FILT_ROWS:
+        _FILT_ROWS[key] = np.random.default_rng([30, sorted(FILTERS).index(name), n]).standard_normal((max(filter_rows(name)), n))
+        _FILT_ROWS[key].setflags(write=False)
+    return _FILT_ROWS[key][idx]
+
+
+def filter_batch_indices(r: int) -> List[int]:
+    """pool rows of a batch of r rows: the first r normal rows, the middle one replaced by 'constant' and the last by 'step'
+    (a batch of one row stays 'normal': the special rows run alone beside it)"""
+    idx = list(range(r))
+    if r >= 3:
+        idx[r // 2] = CONSTANT_ROW
+        idx[r - 1] = STEP_ROW
+    return idx
+
+
+def filter_want(name: str, n: int, idx: int) -> np.ndarray:
+    """O.filtfilt of one pool row, computed once (the Python recurrence is the slow part of these tests)"""
+    key = (name, n, idx)
+    if key not in _FILT_WANT:
+        b, a = FILTERS[name]
+        _FILT_WANT[key] = O.filtfilt(b, a, filter_pool_row(name, n, idx))
+        _FILT_WANT[key].setflags(write=False)
+    return _FILT_WANT[key]
+
+
+RAGGED_R = 70
+
+
+def ragged_case(name: str):
+    """70 rows (two workgroups, the second with 6 of its 64 lanes live) of seeded lengths in 3K+1 .. 3K+400, the minimum and
+    the maximum both present; inputs 3 doubles apart, outputs in permuted order with gaps of 1 .. 5 doubles and a tail.
+    -> (lengths, in_off, out_off, in_buf, out_len, rows)"""
+    k = taps(name)
+    rng = np.random.default_rng([33, k])
+    lengths = rng.integers(3 * k + 1, 3 * k + 401, RAGGED_R).astype(np.int32)
+    lengths[5] = 3 * k + 1
+    lengths[RAGGED_R - 2] = 3 * k + 400                             # (in the partly filled second workgroup)
+    assert int(lengths.max()) - int(lengths.min()) > 4 * 64
+    rows = [np.ascontiguousarray(rng.standard_normal(int(n))) for n in lengths]
+    rows[7] = family("constant", [34, k], int(lengths[7]))
+    rows[66] = family("step", [35, k], int(lengths[66]))
+    in_off = np.zeros(RAGGED_R, dtype=np.int64)
+    pos = 3
+    for r in range(RAGGED_R):
+        in_off[r] = pos
+        pos += int(lengths[r]) + 3
+    in_buf = np.full(pos, SENTINEL)
+    for r in range(RAGGED_R):
+        in_buf[in_off[r]: in_off[r] + lengths[r]] = rows[r]
+    out_off = np.zeros(RAGGED_R, dtype=np.int64)
+    pos = 2
+    for r in rng.permutation(RAGGED_R):
+        out_off[r] = pos
+        pos += int(lengths[r]) + 1 + int(rng.integers(0, 5))
+    return lengths, in_off, out_off, in_buf, pos + 64, rows

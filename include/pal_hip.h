@@ -278,6 +278,29 @@ int pal_wiener3_dev(pal_handle h, const double* d_rows, int R, int N, double* d_
 int pal_filtfilt_ragged_dev(pal_handle h, const double* b, int nb, const double* a, int na, const double* zi, const double* d_in,
                             double* d_out, int R, const int64_t* in_off, const int64_t* out_off, const int32_t* lengths);
 
+/* ---- recorded audio: resample, normalise, cut frames (utils.py:459-482 in front of the stage chain above) ---------------
+ * pal_resample: signal_processing.resample_kaiser_best along the rows of rows[R][N] -> out[R][n_out], n_out = (int)(N * ratio),
+ *   ratio = target_fs / original_fs, bit for bit the host function's result (one lane per output sample, the filter taps in
+ *   the host function's order, every product rounded before it is added).  n_out_capacity: samples per row that `out` holds;
+ *   *n_out is set whenever the rates and N are valid, also when the capacity is too small (PAL_ERR_INVALID) and when `out` is
+ *   NULL (a length query: nothing runs).  A rate that is not positive or n_out < 1: PAL_ERR_INVALID.  Ratios whose output
+ *   would reach 2^31 samples per row: PAL_ERR_UNSUPPORTED.  pal_resample_dev: rows and out in HBM, asynchronous.
+ * pal_resample_set_filter: the right wing of the interpolation filter (win[nwin], num_table entries per zero crossing) as
+ *   the host function builds it (_kaiser_best_filter: SciPy's Kaiser window x NumPy's sinc - the engine takes the table
+ *   instead of restating those two, so that both sides hold the same bits).  Once per engine, before the first resample;
+ *   the engine derives the scaled (win, delta) table of a ratio from it and keeps the latest one in HBM.
+ * pal_normalize_compress_dev: pal_normalize_compress on d_rows[R][N] -> d_out[R][N] in HBM (d_out may be d_rows).
+ * pal_frame_rows_dev: d_out[f][m][i] = d_rows[m][(first_frame + f) * hop + i] for f < F, m < M, i < frame_len (d_rows[M][T]);
+ *   PAL_ERR_INVALID when the last frame would read past T. */
+int pal_resample_set_filter(pal_handle h, const double* win, int nwin, int num_table);
+int pal_resample(pal_handle h, const double* rows, int R, int N, double original_fs, double target_fs, double* out, int n_out_capacity,
+                 int* n_out);
+int pal_resample_dev(pal_handle h, const double* d_rows, int R, int N, double original_fs, double target_fs, double* d_out,
+                     int n_out_capacity, int* n_out);
+int pal_normalize_compress_dev(pal_handle h, const double* d_rows, int R, int N, int normalize_only, double threshold, double epsilon,
+                               double* d_out);
+int pal_frame_rows_dev(pal_handle h, const double* d_rows, int M, int T, int frame_len, int hop, int first_frame, int F, double* d_out);
+
 /* ---- multi-GPU: one gather of the TDOA table over RCCL/xGMI ------------------------------ */
 int pal_comm_unique_id(void* id128);                       /* rank 0; 128-byte ncclUniqueId          */
 int pal_comm_init(pal_handle h, int nranks, int rank, const void* id128);

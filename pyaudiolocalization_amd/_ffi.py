@@ -105,6 +105,11 @@ SIGNATURES = {
     "pal_wiener3_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "pal_filtfilt_ragged_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pal_resample_set_filter": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int]),
+    "pal_resample": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "pal_resample_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "pal_normalize_compress_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
+    "pal_frame_rows_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pal_comm_unique_id": (C.c_int, [C.c_void_p]),
     "pal_comm_init": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
     "pal_comm_all_gather": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t]),

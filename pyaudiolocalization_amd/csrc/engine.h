@@ -15,6 +15,7 @@
 #include "fft_core.h"
 #include "pair_route.h"
 #include "peak_types.h"
+#include "resample_math.h"
 
 namespace pal {
 
@@ -96,7 +97,8 @@ enum Ws : int {
   kWsFlags = 19, kWsFlagQuads = 20, kWsFlagTable = 21,  // its flagged pairs: [flags | list | count], their packed transforms, their repaired records
   kWsSolve = 22,       // the position solve (solve.hip): uploaded small inputs, (b, w) per pair, starts, per-start results, records
   kWsBlockTable = 23,  // (caller) records in blocked pair order (all_pairs_dev, large arrays)
-  kWsCount = 24
+  kWsResample = 24,    // resample.hip: the interleaved (win, delta) filter table of the latest ratio
+  kWsCount = 25
 };
 constexpr Ws peak_scratch_slot(int slot) { return slot == 0 ? kWsPeaks0 : (slot == 1 ? kWsPeaks1 : kWsPeaks2); }
 constexpr Ws fin_scratch_slot(int slot) { return Ws(kWsFin0 + slot); }
@@ -219,6 +221,12 @@ struct Engine {
                           const double* weights, const double* extra_starts, const pal_solve_params* prm, pal_position_record* out);
   int32_t* solve_idx = nullptr;    // device table pair -> i | j << 16 of the last microphone count
   int solve_idx_M = 0;
+  // resample.hip: the right wing of the interpolation filter as pal_resample_set_filter received it, and the ratio whose scaled
+  // (win, delta) table sits in kWsResample (0: none yet)
+  std::vector<double> rs_win;
+  std::vector<ResampleTap> rs_host;   // the table's host copy (source of its upload)
+  int rs_num_table = 0;
+  double rs_ratio = 0;
   int peaks(const double* corr, size_t stride, int rows, int n, int n2, const pal_phat_params& prm,
             pal_pair_record* table, int32_t* ksel_multi, int slot);
   // the same in pieces, for the column pass that produces the streaming statistics itself (pfa_cols_stats.h):

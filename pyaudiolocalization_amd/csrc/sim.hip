@@ -557,6 +557,18 @@ int pal_normalize_compress(pal_handle h, const double* rows_in, int R, int N, in
   return pal_synchronize(h);
 }
 
+int pal_normalize_compress_dev(pal_handle h, const double* d_rows, int R, int N, int normalize_only, double threshold, double epsilon,
+                               double* d_out) {
+  ENGINE(h);
+  if (!d_rows || !d_out || R < 1 || N < 1) return e->fail(PAL_ERR_INVALID, "bad normalize arguments");
+  {
+    ProfScope ps(e, "k_norm_compress");
+    k_norm_compress<<<dim3(R), dim3(kLanes), 0, e->stream>>>(d_rows, size_t(N), d_out, size_t(N), N, normalize_only, threshold, epsilon,
+                                                            nullptr, 0);
+  }
+  return e->check(hipGetLastError(), "k_norm_compress");
+}
+
 int pal_filtfilt(pal_handle h, const double* b, int nb, const double* a, int na, const double* zi, const double* rows_in,
                  int R, int N, double* out) {
   ENGINE(h);

@@ -439,6 +439,64 @@ class Engine:
     def wiener3_dev(self, d_rows: int, r: int, n: int, d_out: int) -> None:
         self._check(self._lib.pal_wiener3_dev(self._h, C.c_void_p(d_rows), int(r), int(n), C.c_void_p(d_out)))
 
+    # ---- recorded audio: resample, normalise, cut frames (stream.recorded_tdoa_stream) -------------
+    def resample_set_filter(self, win, num_table: int) -> None:
+        """The right wing of the interpolation filter and its table entries per zero crossing (once per engine)."""
+        w = f64(win)
+        if w.ndim != 1:
+            raise ValueError("the filter wing is one-dimensional")
+        self._check(self._lib.pal_resample_set_filter(self._h, w.ctypes.data, w.shape[0], int(num_table)))
+        self._resample_filter = True
+
+    def _resample_length(self, n: int, original_fs, target_fs) -> int:
+        """Output length and errors of signal_processing.resample_kaiser_best; hands the engine the filter on first use."""
+        ratio = float(target_fs) / float(original_fs)
+        if ratio <= 0:
+            raise ValueError("Invalid sample rates")
+        n_out = int(n * ratio)
+        if n_out < 1:
+            raise ValueError(f"Input signal length={n} is too small to resample from {original_fs}->{target_fs}")
+        if not getattr(self, "_resample_filter", False):
+            from .signal_processing import _kaiser_best_filter  # noqa: PLC0415 - signal_processing imports this module
+            self.resample_set_filter(*_kaiser_best_filter())
+        return n_out
+
+    def resample(self, rows, original_fs, target_fs) -> np.ndarray:
+        """signal_processing.resample_kaiser_best along the last axis of rows[R][N] (or [N]) on the device, bit for bit."""
+        x = f64(rows)
+        if x.ndim == 0:
+            raise ValueError("rows must have a sample axis")
+        lead, n = x.shape[:-1], x.shape[-1]
+        n_out = self._resample_length(n, original_fs, target_fs)
+        x2 = x.reshape(-1, n)
+        out = np.empty((x2.shape[0], n_out))
+        if x2.shape[0] == 0:
+            return out.reshape(lead + (n_out,))
+        got = C.c_int()
+        self._check(self._lib.pal_resample(self._h, x2.ctypes.data, x2.shape[0], n, float(original_fs), float(target_fs), out.ctypes.data,
+                                           n_out, C.byref(got)))
+        assert got.value == n_out
+        return out.reshape(lead + (n_out,))
+
+    def resample_dev(self, d_rows: int, r: int, n: int, original_fs, target_fs, d_out: int, n_out_capacity: int) -> int:
+        """Asynchronous: d_rows[r][n] -> d_out[r][n_out] in HBM; returns n_out = int(n * target_fs / original_fs)."""
+        n_out = self._resample_length(int(n), original_fs, target_fs)
+        got = C.c_int()
+        self._check(self._lib.pal_resample_dev(self._h, C.c_void_p(d_rows), int(r), int(n), float(original_fs), float(target_fs),
+                                               C.c_void_p(d_out), int(n_out_capacity), C.byref(got)))
+        assert got.value == n_out
+        return n_out
+
+    def normalize_compress_dev(self, d_rows: int, r: int, n: int, d_out: int, normalize_only=False, threshold=0.8, epsilon=1e-8) -> None:
+        """Asynchronous: normalize_compress on d_rows[r][n] -> d_out[r][n] in HBM (d_out may be d_rows)."""
+        self._check(self._lib.pal_normalize_compress_dev(self._h, C.c_void_p(d_rows), int(r), int(n), int(normalize_only), float(threshold),
+                                                         float(epsilon), C.c_void_p(d_out)))
+
+    def frame_rows_dev(self, d_rows: int, m: int, t: int, frame_len: int, hop: int, first_frame: int, frames: int, d_out: int) -> None:
+        """Asynchronous: d_out[f][m][i] = d_rows[m][(first_frame + f) * hop + i]; a frame past sample t raises ValueError."""
+        self._check(self._lib.pal_frame_rows_dev(self._h, C.c_void_p(d_rows), int(m), int(t), int(frame_len), int(hop), int(first_frame),
+                                                 int(frames), C.c_void_p(d_out)))
+
     # ---- multi-GPU ---------------------------------------------------------------------
     @staticmethod
     def comm_unique_id() -> bytes:

@@ -144,10 +144,15 @@ def resample_kaiser_best(data: np.ndarray, original_fs: float, target_fs: float)
     return y.reshape(lead + (n_out,))
 
 
-def resample_audio(data: np.ndarray, original_fs: float, target_fs: float) -> np.ndarray:
-    """signal_processing.py:105-107 (outside the hot path): resampy's kaiser_best when that optional package
-    is installed; without it (the build image) the own implementation of the same published algorithm and filter design
-    (`resample_kaiser_best`: parity unpinned, no resampy output exists here to compare with)."""
+def resample_audio(data: np.ndarray, original_fs: float, target_fs: float, resampler: str = "host") -> np.ndarray:
+    """signal_processing.py:105-107.  ``resampler="host"`` (the default): resampy's kaiser_best when that optional
+    package is installed; without it (the build image) the own implementation of the same published algorithm and filter design
+    (`resample_kaiser_best`: parity unpinned, no resampy output exists here to compare with).  ``resampler="device"``:
+    `resample_kaiser_best` on the engine (Engine.resample: the same bits as the host function, one lane per output sample)."""
+    if resampler == "device":
+        return default_engine().resample(data, original_fs, target_fs)
+    if resampler != "host":
+        raise ValueError("resampler: 'host' or 'device'")
     try:
         import resampy  # noqa: PLC0415 - optional dependency
         return resampy.resample(data, original_fs, target_fs, filter="kaiser_best")

@@ -436,10 +436,13 @@ def _read_wav_pcm(path: str) -> Tuple[np.ndarray, int]:
     return (x.reshape(-1, channels) if channels > 1 else x), fs
 
 
-def read_audio_files(audio_files: List[str], expected_fs: float) -> List[np.ndarray]:
+def read_audio_files(audio_files: List[str], expected_fs: float, resampler: str = "host") -> List[np.ndarray]:
     """Real-audio ingest (utils.py:459-482; SURVEY 8f N4, outside the hot path): mono mix, resample to `expected_fs`,
     normalise, compress.  Decoding uses the optional soundfile package when it is installed and the standard library's
-    PCM WAV reader otherwise (the build image has neither soundfile nor resampy)."""
+    PCM WAV reader otherwise (the build image has neither soundfile nor resampy).  ``resampler``: as resample_audio ("device"
+    resamples on the engine)."""
+    if resampler not in ("host", "device"):
+        raise ValueError("resampler: 'host' or 'device'")
     from .signal_processing import dynamic_range_compression, normalize_signal, resample_audio
     out = []
     for path in audio_files:
@@ -455,7 +458,7 @@ def read_audio_files(audio_files: List[str], expected_fs: float) -> List[np.ndar
             if data.ndim > 1:
                 data = np.mean(data, axis=1)
             if fs != expected_fs:
-                data = resample_audio(data, fs, expected_fs)
+                data = resample_audio(data, fs, expected_fs, resampler)
             out.append(dynamic_range_compression(normalize_signal(data)))
         except Exception as exc:
             log.error("error reading audio file '%s': %s", path, exc)

@@ -200,6 +200,21 @@ int pal_solve_positions_dev(pal_handle h, const pal_pair_record* d_tables, int B
 int pal_solve_positions(pal_handle h, const pal_pair_record* tables, int B, int M, const int32_t* lengths, const double* mics,
                         const double* calib, const double* weights, const double* extra_starts, const pal_solve_params* prm,
                         pal_position_record* out);
+/* The same solve under a robust loss, for tables with outlier pairs: minimise sum_p C^2 rho(r_p^2 / C^2) / 2 (SciPy's convention;
+ * `cost` of the record is that sum) with C = f_scale in metres of weighted residual, finite and positive, and rho(z) = z (LINEAR:
+ * the two calls above, f_scale ignored), 2 (sqrt(1 + z) - 1), z | 2 sqrt(z) - 1 beyond z = 1, or ln(1 + z).  pair_weights[B][P]
+ * (host, or NULL) receives rho'(z_p) at the returned position: 1 for a pair the fit kept, towards 0 for one it discounted.
+ * An unknown loss or a bad f_scale is PAL_ERR_INVALID. */
+#define PAL_SOLVE_LOSS_LINEAR 0
+#define PAL_SOLVE_LOSS_SOFT_L1 1
+#define PAL_SOLVE_LOSS_HUBER 2
+#define PAL_SOLVE_LOSS_CAUCHY 3
+int pal_solve_positions_loss_dev(pal_handle h, const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics,
+                                 const double* calib, const double* weights, const double* extra_starts, const pal_solve_params* prm,
+                                 pal_position_record* out, int32_t loss, double f_scale, double* pair_weights);
+int pal_solve_positions_loss(pal_handle h, const pal_pair_record* tables, int B, int M, const int32_t* lengths, const double* mics,
+                             const double* calib, const double* weights, const double* extra_starts, const pal_solve_params* prm,
+                             pal_position_record* out, int32_t loss, double f_scale, double* pair_weights);
 
 /* single-pair signatures: phat_correlation(sig1, sig2) (utils.py:108) -> corr[n1+n2-1] */
 int pal_phat_correlation(pal_handle h, const double* sig1, int n1, const double* sig2, int n2, double* corr);

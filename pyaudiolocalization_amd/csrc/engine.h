@@ -219,6 +219,13 @@ struct Engine {
   // solve.hip: TDOA tables -> positions (d_tables in HBM, every other argument a host array); returns with `out` filled
   int solve_positions_dev(const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics, const double* calib,
                           const double* weights, const double* extra_starts, const pal_solve_params* prm, pal_position_record* out);
+  // the same under a robust loss (PAL_SOLVE_LOSS_*, scale f_scale); pair_weights[B][P] (host, or nullptr): rho'(z) of every pair
+  int solve_positions_loss_dev(const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics, const double* calib,
+                               const double* weights, const double* extra_starts, const pal_solve_params* prm, pal_position_record* out,
+                               int loss, double f_scale, double* pair_weights);
+  int solve_positions_impl(const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics, const double* calib,
+                           const double* weights, const double* extra_starts, const pal_solve_params* prm, pal_position_record* out,
+                           int loss, double f_scale, double* pair_weights);
   int32_t* solve_idx = nullptr;    // device table pair -> i | j << 16 of the last microphone count
   int solve_idx_M = 0;
   // resample.hip: the right wing of the interpolation filter as pal_resample_set_filter received it, and the ratio whose scaled

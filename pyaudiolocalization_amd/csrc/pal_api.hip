@@ -527,6 +527,35 @@ int pal_solve_positions(pal_handle h, const pal_pair_record* tables, int B, int 
   return e->solve_positions_dev(static_cast<const pal_pair_record*>(dt), B, M, lengths, mics, calib, weights, extra_starts, prm, out);
 }
 
+int pal_solve_positions_loss_dev(pal_handle h, const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics,
+                                 const double* calib, const double* weights, const double* extra_starts, const pal_solve_params* prm,
+                                 pal_position_record* out, int32_t loss, double f_scale, double* pair_weights) {
+  ENGINE(h);
+  return e->solve_positions_loss_dev(d_tables, B, M, lengths, mics, calib, weights, extra_starts, prm, out, loss, f_scale, pair_weights);
+}
+
+int pal_solve_positions_loss(pal_handle h, const pal_pair_record* tables, int B, int M, const int32_t* lengths, const double* mics,
+                             const double* calib, const double* weights, const double* extra_starts, const pal_solve_params* prm,
+                             pal_position_record* out, int32_t loss, double f_scale, double* pair_weights) {
+  ENGINE(h);
+  if (!tables) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  if (B < 1) return e->fail(PAL_ERR_INVALID, "need B >= 1");
+  if (M < 2) return e->fail(PAL_ERR_INVALID, "need at least 2 microphones (got %d)", M);
+  if (loss < PAL_SOLVE_LOSS_LINEAR || loss > PAL_SOLVE_LOSS_CAUCHY) return e->fail(PAL_ERR_INVALID, "unknown loss %d", loss);
+  if (!(std::isfinite(f_scale) && f_scale > 0)) return e->fail(PAL_ERR_INVALID, "f_scale must be finite and positive");
+  if (loss == PAL_SOLVE_LOSS_LINEAR) {
+    const int rc = pal_solve_positions(h, tables, B, M, lengths, mics, calib, weights, extra_starts, prm, out);
+    if (rc == PAL_OK && pair_weights) std::fill(pair_weights, pair_weights + size_t(B) * (size_t(M) * size_t(M - 1) / 2), 1.0);
+    return rc;
+  }
+  const size_t bytes = size_t(B) * size_t(M) * size_t(M - 1) / 2 * sizeof(pal_pair_record);
+  void* dt = nullptr;
+  PAL_TRY(e->scratch(kWsStageTable, bytes, &dt));
+  PAL_TRY(e->check(hipMemcpyAsync(dt, tables, bytes, hipMemcpyHostToDevice, e->stream), "tables upload"));
+  return e->solve_positions_loss_dev(static_cast<const pal_pair_record*>(dt), B, M, lengths, mics, calib, weights, extra_starts, prm, out, loss,
+                                     f_scale, pair_weights);
+}
+
 static int single_pair(Engine* e, const double* sig1, int n1, const double* sig2, int n2, const pal_phat_params* prm,
                        int32_t* k_out, pal_pair_record* rec, double* corr) {
   if (!sig1 || !sig2) return e->fail(PAL_ERR_INVALID, "NULL signal");

@@ -8,7 +8,11 @@
 //                    one LDS hop over the wavefronts in a fixed order; every lane then runs the 3 x 3 solve and the bookkeeping
 //                    on the same values, so the workgroup needs no broadcast and a result never depends on the batch;
 //   k_solve_pick     one wavefront per frame: the winner among the starts.
+// A robust loss (pal_solve_positions_loss*; solve.lm_solve_loss) runs k_solve_lm's instantiation for that loss - nineteen sums,
+// the pairs reweighted by rho'(z) and rho'(z) + 2 z rho''(z) - and, when the caller asks which pairs the fit discounted,
+//   k_solve_weights  one workgroup per frame: rho'(z_p) of every pair at the winning position.
 // No floating-point atomics, no waits between workgroups.
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -44,9 +48,12 @@ struct SolveArgs {
   SolveFrame* frames;              // [B]
   SolveStart* results;             // [B][S]
   pal_position_record* out;        // [B]
+  double* pair_weights;            // [B][P] or nullptr (robust losses only)
   int B, M, P, S;
   int grid, n_extra, max_iter, weight_mode;
   double fs, c, buffer;
+  double c2, inv_c2;               // f_scale^2 and its reciprocal (robust losses only)
+  int loss;
 };
 
 constexpr int kPrepThreads = 256;
@@ -168,13 +175,14 @@ __global__ __launch_bounds__(kPrepThreads) void k_solve_prepare(SolveArgs a) {
 }
 
 // One workgroup of T lanes per (frame, start).  LDS: the microphones (6 KB at M = 256), their ten terms at the trial point
-// (20 KB), the wavefronts' partial sums.
-template <int T>
+// (20 KB), the wavefronts' partial sums.  LOSS: sv::kLossLinear is the sum of squares on sixteen sums; a robust loss carries nineteen.
+template <int T, int LOSS = sv::kLossLinear>
 __global__ __launch_bounds__(T) void k_solve_lm(SolveArgs a) {
   constexpr int W = T / 64;
+  constexpr int NS = LOSS == sv::kLossLinear ? sv::kSums : sv::kSumsLoss;
   __shared__ double mic[sv::kMaxMics * 3];
   __shared__ double terms[sv::kMaxMics * sv::kMicTerms];
-  __shared__ double red[W * sv::kSums];
+  __shared__ double red[W * NS];
   const int b = blockIdx.x / a.S, s = blockIdx.x % a.S, tid = threadIdx.x, P = a.P, M = a.M;
   SolveStart* res = a.results + size_t(b) * a.S + s;
   const SolveFrame fr = a.frames[b];
@@ -195,32 +203,35 @@ __global__ __launch_bounds__(T) void k_solve_lm(SolveArgs a) {
     __syncthreads();                                   // the previous point's readers are done (first call: mic[] is written)
     for (int m = tid; m < M; m += T) sv::mic_terms(x, mic + 3 * m, terms + sv::kMicTerms * m);
     __syncthreads();
-    double acc[sv::kSums];
+    double acc[NS];
 #pragma unroll
-    for (int q = 0; q < sv::kSums; ++q) acc[q] = 0.0;
+    for (int q = 0; q < NS; ++q) acc[q] = 0.0;
     for (int p = tid; p < P; p += T) {
       const double2 v = bw[p];
       const int ij = idx[p];
-      sv::pair_accumulate(acc, terms + sv::kMicTerms * (ij & 0xffff), terms + sv::kMicTerms * (ij >> 16), v.x, v.y);
+      const double *ti = terms + sv::kMicTerms * (ij & 0xffff), *tj = terms + sv::kMicTerms * (ij >> 16);
+      if constexpr (LOSS == sv::kLossLinear) sv::pair_accumulate(acc, ti, tj, v.x, v.y);
+      else sv::pair_accumulate_loss<LOSS>(acc, ti, tj, v.x, v.y, a.inv_c2);
     }
 #pragma unroll
-    for (int q = 0; q < sv::kSums; ++q) {
+    for (int q = 0; q < NS; ++q) {
       const double r = wave_sum63(acc[q]);
-      if ((tid & 63) == 63) red[(tid >> 6) * sv::kSums + q] = r;
+      if ((tid & 63) == 63) red[(tid >> 6) * NS + q] = r;
     }
     __syncthreads();
 #pragma unroll
-    for (int q = 0; q < sv::kSums; ++q) {
+    for (int q = 0; q < NS; ++q) {
       double r = red[q];
 #pragma unroll
-      for (int w = 1; w < W; ++w) r += red[w * sv::kSums + q];
+      for (int w = 1; w < W; ++w) r += red[w * NS + q];
       out[q] = r;
     }
+    if constexpr (LOSS != sv::kLossLinear) out[15] = a.c2 * out[15];      // C^2 sum rho(z) in place of rtr
   };
   const double* x0 = a.starts + (size_t(b) * a.S + s) * 3;
   const double start[3] = {x0[0], x0[1], x0[2]};
   SolveStart r;
-  sv::lm_solve(start, fr.lo, fr.hi, a.max_iter, eval, r.x, &r.cost, &r.iters, &r.stop);
+  sv::lm_solve<NS>(start, fr.lo, fr.hi, a.max_iter, eval, r.x, &r.cost, &r.iters, &r.stop);
   if (tid == 0) *res = r;
 }
 
@@ -278,10 +289,51 @@ __global__ __launch_bounds__(64) void k_solve_pick(SolveArgs a) {
   a.out[b] = o;
 }
 
+// rho'(z_p) of every pair at the frame's winning position (NaN where the frame has none): one workgroup per frame, the
+// microphones' distances in LDS.
+constexpr int kWeightThreads = 256;
+__global__ __launch_bounds__(kWeightThreads) void k_solve_weights(SolveArgs a) {
+  __shared__ double dist[sv::kMaxMics];
+  const int b = blockIdx.x, tid = threadIdx.x, P = a.P;
+  const double* x = a.out[b].position;
+  for (int m = tid; m < a.M; m += kWeightThreads) {
+    const double dx = x[0] - a.mics[3 * m], dy = x[1] - a.mics[3 * m + 1], dz = x[2] - a.mics[3 * m + 2];
+    dist[m] = sqrt(dx * dx + dy * dy + dz * dz);
+  }
+  __syncthreads();
+  const double2* bw = a.bw + size_t(b) * P;
+  double* dst = a.pair_weights + size_t(b) * P;
+  for (int p = tid; p < P; p += kWeightThreads) {
+    const double2 v = bw[p];
+    const int ij = a.pair_idx[p];
+    const double r = (dist[ij >> 16] - dist[ij & 0xffff]) * v.y - v.x;
+    dst[p] = sv::loss_d1_of(a.loss, (r * r) * a.inv_c2);
+  }
+}
+
 static size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 
 int Engine::solve_positions_dev(const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics, const double* calib,
                                 const double* weights, const double* extra_starts, const pal_solve_params* prm, pal_position_record* out) {
+  return solve_positions_impl(d_tables, B, M, lengths, mics, calib, weights, extra_starts, prm, out, sv::kLossLinear, 1.0, nullptr);
+}
+
+int Engine::solve_positions_loss_dev(const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics, const double* calib,
+                                     const double* weights, const double* extra_starts, const pal_solve_params* prm, pal_position_record* out,
+                                     int loss, double f_scale, double* pair_weights) {
+  if (loss < PAL_SOLVE_LOSS_LINEAR || loss > PAL_SOLVE_LOSS_CAUCHY) return fail(PAL_ERR_INVALID, "unknown loss %d", loss);
+  if (!(std::isfinite(f_scale) && f_scale > 0)) return fail(PAL_ERR_INVALID, "f_scale must be finite and positive");
+  if (loss != PAL_SOLVE_LOSS_LINEAR)
+    return solve_positions_impl(d_tables, B, M, lengths, mics, calib, weights, extra_starts, prm, out, loss, f_scale, pair_weights);
+  const int rc = solve_positions_dev(d_tables, B, M, lengths, mics, calib, weights, extra_starts, prm, out);
+  if (rc == PAL_OK && pair_weights) std::fill(pair_weights, pair_weights + size_t(B) * (size_t(M) * size_t(M - 1) / 2), 1.0);
+  return rc;
+}
+
+// loss = sv::kLossLinear takes the sum-of-squares kernels and ignores f_scale and pair_weights
+int Engine::solve_positions_impl(const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics, const double* calib,
+                                 const double* weights, const double* extra_starts, const pal_solve_params* prm, pal_position_record* out,
+                                 int loss, double f_scale, double* pair_weights) {
   if (!d_tables || !lengths || !mics || !prm || !out) return fail(PAL_ERR_INVALID, "NULL buffer");
   if (B < 1) return fail(PAL_ERR_INVALID, "need B >= 1");
   if (M < 2) return fail(PAL_ERR_INVALID, "need at least 2 microphones (got %d)", M);
@@ -313,7 +365,8 @@ int Engine::solve_positions_dev(const pal_pair_record* d_tables, int B, int M, c
     PAL_HIP(hipStreamSynchronize(stream));
     solve_idx_M = M;
   }
-  // one scratch block: [lengths | mics | calib | weights | extra | bw | v | starts | frames | results | out]
+  const bool want_pw = loss != sv::kLossLinear && pair_weights;
+  // one scratch block: [lengths | mics | calib | weights | extra | bw | v | starts | frames | results | out | pair weights]
   const size_t np = size_t(B) * size_t(P);
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t at = off; off = align256(off + bytes); return at; };
@@ -324,6 +377,7 @@ int Engine::solve_positions_dev(const pal_pair_record* d_tables, int B, int M, c
   const size_t o_bw = take(np * sizeof(double2)), o_v = take(np * sizeof(double));
   const size_t o_st = take(size_t(B) * S * 3 * sizeof(double)), o_fr = take(size_t(B) * sizeof(SolveFrame));
   const size_t o_res = take(size_t(B) * S * sizeof(SolveStart)), o_out = take(size_t(B) * sizeof(pal_position_record));
+  const size_t o_pw = take(want_pw ? np * sizeof(double) : 0);
   char* base = nullptr;
   PAL_TRY(scratch(kWsSolve, off, &base));
   PAL_HIP(hipMemcpyAsync(base + o_len, lengths, size_t(B) * sizeof(int32_t), hipMemcpyHostToDevice, stream));
@@ -349,17 +403,33 @@ int Engine::solve_positions_dev(const pal_pair_record* d_tables, int B, int M, c
   a.B = B; a.M = M; a.P = P; a.S = S;
   a.grid = prm->grid; a.n_extra = prm->n_extra; a.max_iter = prm->max_iter > 0 ? prm->max_iter : sv::kMaxIter; a.weight_mode = prm->weight_mode;
   a.fs = prm->fs; a.c = prm->c; a.buffer = prm->buffer;
+  a.pair_weights = want_pw ? reinterpret_cast<double*>(base + o_pw) : nullptr;
+  a.c2 = f_scale * f_scale; a.inv_c2 = 1.0 / a.c2; a.loss = loss;
   {
     ProfScope ps(this, "k_solve_prepare");
     k_solve_prepare<<<dim3(unsigned(B)), dim3(kPrepThreads), 0, stream>>>(a);
   }
   PAL_HIP(hipGetLastError());
-  if (P <= 512) {           // a wavefront covers a small table (6 / 28 pairs at 4 / 8 microphones) in one to eight strides
-    ProfScope ps(this, "k_solve_lm<64>");
-    k_solve_lm<64><<<dim3(unsigned(B * S)), dim3(64), 0, stream>>>(a);
+  const dim3 lm_grid(unsigned(B * S));
+  if (loss == sv::kLossLinear) {
+    if (P <= 512) {           // a wavefront covers a small table (6 / 28 pairs at 4 / 8 microphones) in one to eight strides
+      ProfScope ps(this, "k_solve_lm<64>");
+      k_solve_lm<64><<<lm_grid, dim3(64), 0, stream>>>(a);
+    } else {
+      ProfScope ps(this, "k_solve_lm<256>");
+      k_solve_lm<256><<<lm_grid, dim3(256), 0, stream>>>(a);
+    }
   } else {
-    ProfScope ps(this, "k_solve_lm<256>");
-    k_solve_lm<256><<<dim3(unsigned(B * S)), dim3(256), 0, stream>>>(a);
+    ProfScope ps(this, P <= 512 ? "k_solve_lm<64, loss>" : "k_solve_lm<256, loss>");
+    if (P <= 512) {
+      if (loss == sv::kLossSoftL1) k_solve_lm<64, sv::kLossSoftL1><<<lm_grid, dim3(64), 0, stream>>>(a);
+      else if (loss == sv::kLossHuber) k_solve_lm<64, sv::kLossHuber><<<lm_grid, dim3(64), 0, stream>>>(a);
+      else k_solve_lm<64, sv::kLossCauchy><<<lm_grid, dim3(64), 0, stream>>>(a);
+    } else {
+      if (loss == sv::kLossSoftL1) k_solve_lm<256, sv::kLossSoftL1><<<lm_grid, dim3(256), 0, stream>>>(a);
+      else if (loss == sv::kLossHuber) k_solve_lm<256, sv::kLossHuber><<<lm_grid, dim3(256), 0, stream>>>(a);
+      else k_solve_lm<256, sv::kLossCauchy><<<lm_grid, dim3(256), 0, stream>>>(a);
+    }
   }
   PAL_HIP(hipGetLastError());
   {
@@ -367,6 +437,14 @@ int Engine::solve_positions_dev(const pal_pair_record* d_tables, int B, int M, c
     k_solve_pick<<<dim3(unsigned(B)), dim3(64), 0, stream>>>(a);
   }
   PAL_HIP(hipGetLastError());
+  if (want_pw) {
+    {
+      ProfScope ps(this, "k_solve_weights");
+      k_solve_weights<<<dim3(unsigned(B)), dim3(kWeightThreads), 0, stream>>>(a);
+    }
+    PAL_HIP(hipGetLastError());
+    PAL_HIP(hipMemcpyAsync(pair_weights, base + o_pw, np * sizeof(double), hipMemcpyDeviceToHost, stream));
+  }
   PAL_HIP(hipMemcpyAsync(out, base + o_out, size_t(B) * sizeof(pal_position_record), hipMemcpyDeviceToHost, stream));
   return check(hipStreamSynchronize(stream), "solve sync");
 }

@@ -1,6 +1,6 @@
 // solve_math.h - arithmetic of the batched position solve (solve.hip), host and device: the restatement in C++ of
 // pyaudiolocalization_amd/solve.py (the specification; names and constants follow it).  tests/host/test_solve_math.cpp runs it
-// on the host.
+// on the host, tests/host/test_solve_loss.cpp the robust losses.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -45,6 +45,69 @@ PAL_SOLVE_HD inline void pair_accumulate(double acc[kSums], const double* ti, co
   acc[15] += r * r;
 }
 
+// ---- robust losses (solve.loss_terms): rho, rho' and rho' + 2 z rho'' at z = r^2 / C^2, SciPy's convention.  Written without
+// cancellation at small z; every one is finite (or an exact zero) up to the largest float64.
+enum Loss : int { kLossLinear = 0, kLossSoftL1 = 1, kLossHuber = 2, kLossCauchy = 3 };
+// sums of a robust loss at a point: [0..5] sum c j j^t, [6..11] sum a r w (H_j - H_i), [12..14] the gradient sum a r j,
+// [15] C^2 sum rho(z), [16..18] sum a j_k^2 (Marquardt's diagonal), with a = rho', c = max(rho' + 2 z rho'', 0)
+constexpr int kSumsLoss = 19;
+
+template <int LOSS> PAL_SOLVE_HD inline double loss_rho(double z) {
+  if (LOSS == kLossSoftL1) return 2.0 * z / (sqrt(1.0 + z) + 1.0);       // 2 (sqrt(1 + z) - 1)
+  if (LOSS == kLossHuber) return z <= 1.0 ? z : 2.0 * sqrt(z) - 1.0;
+  if (LOSS == kLossCauchy) return log1p(z);
+  return z;
+}
+template <int LOSS> PAL_SOLVE_HD inline double loss_d1(double z) {
+  if (LOSS == kLossSoftL1) return 1.0 / sqrt(1.0 + z);
+  if (LOSS == kLossHuber) return z <= 1.0 ? 1.0 : 1.0 / sqrt(z);
+  if (LOSS == kLossCauchy) return 1.0 / (1.0 + z);
+  return 1.0;
+}
+// rho' + 2 z rho'', not clamped: (1 + z)^-3/2, 1 | 0, (1 - z) / (1 + z)^2
+template <int LOSS> PAL_SOLVE_HD inline double loss_curv(double z) {
+  if (LOSS == kLossSoftL1) return 1.0 / sqrt(1.0 + z) / (1.0 + z);
+  if (LOSS == kLossHuber) return z <= 1.0 ? 1.0 : 0.0;
+  if (LOSS == kLossCauchy) { const double a = 1.0 / (1.0 + z); return (1.0 - z) * a * a; }
+  return 1.0;
+}
+// all three with the shared square root or reciprocal computed once: (rho, a, c = max(curv, 0))
+template <int LOSS> PAL_SOLVE_HD inline void loss_terms(double z, double* rho, double* a, double* c) {
+  if (LOSS == kLossSoftL1) {
+    const double t = sqrt(1.0 + z), ia = 1.0 / t;
+    *rho = 2.0 * z / (t + 1.0); *a = ia; *c = ia / (1.0 + z);
+  } else if (LOSS == kLossHuber) {
+    const bool inner = z <= 1.0;
+    const double t = sqrt(inner ? 1.0 : z);
+    *rho = inner ? z : 2.0 * t - 1.0; *a = inner ? 1.0 : 1.0 / t; *c = inner ? 1.0 : 0.0;
+  } else if (LOSS == kLossCauchy) {
+    const double ia = 1.0 / (1.0 + z);
+    *rho = log1p(z); *a = ia; *c = fmax((1.0 - z) * ia * ia, 0.0);
+  } else {
+    *rho = z; *a = 1.0; *c = 1.0;
+  }
+}
+PAL_SOLVE_HD inline double loss_d1_of(int loss, double z) {
+  return loss == kLossSoftL1 ? loss_d1<kLossSoftL1>(z) : loss == kLossHuber ? loss_d1<kLossHuber>(z) : loss == kLossCauchy ? loss_d1<kLossCauchy>(z) : 1.0;
+}
+
+// one pair under a robust loss; inv_c2 = 1 / C^2.  acc[15] collects rho(z): the caller scales the finished sum by C^2.
+template <int LOSS>
+PAL_SOLVE_HD inline void pair_accumulate_loss(double acc[kSumsLoss], const double* ti, const double* tj, double b, double w, double inv_c2) {
+  const double r = (tj[0] - ti[0]) * w - b;
+  const double jx = (tj[1] - ti[1]) * w, jy = (tj[2] - ti[2]) * w, jz = (tj[3] - ti[3]) * w;
+  double rho, a, c;
+  loss_terms<LOSS>((r * r) * inv_c2, &rho, &a, &c);
+  const double ar = a * r, arw = ar * w;
+  const double cx = c * jx, cy = c * jy, cz = c * jz;
+  acc[0] += cx * jx; acc[1] += cx * jy; acc[2] += cx * jz; acc[3] += cy * jy; acc[4] += cy * jz; acc[5] += cz * jz;
+#pragma unroll
+  for (int q = 0; q < 6; ++q) acc[6 + q] += arw * (tj[4 + q] - ti[4 + q]);
+  acc[12] += jx * ar; acc[13] += jy * ar; acc[14] += jz * ar;
+  acc[15] += rho;
+  acc[16] += a * (jx * jx); acc[17] += a * (jy * jy); acc[18] += a * (jz * jz);
+}
+
 // (H + lam diag(d3)) delta = -g on the free coordinates (held: delta = 0), LDLt without pivoting; false when a pivot is not positive
 PAL_SOLVE_HD inline bool damped_step(const double h6[6], const double d3[3], const double g[3], double lam, const bool held[3], double delta[3]) {
   double m00 = h6[0] + lam * d3[0], m01 = h6[1], m02 = h6[2], m11 = h6[3] + lam * d3[1], m12 = h6[4], m22 = h6[5] + lam * d3[2];
@@ -74,11 +137,13 @@ PAL_SOLVE_HD inline double quad_form(const double h6[6], const double s[3]) {
 PAL_SOLVE_HD inline double clip(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
 
 // solve.lm_solve.  eval(x, sums) fills the sixteen sums at x (on the device: the whole workgroup calls it together and every lane
-// receives the same values, so every lane takes the same path).
-template <class Eval>
+// receives the same values, so every lane takes the same path).  NS = kSumsLoss is solve.lm_solve_loss: the same iteration on
+// the nineteen sums of a robust loss, the diagonal taken from sums [16..18].
+template <int NS = kSums, class Eval>
 PAL_SOLVE_HD inline void lm_solve(const double x0[3], const double lo[3], const double hi[3], int max_iter, Eval&& eval, double x[3], double* cost,
                             int* iters, int* stop_rule) {
-  double cur[kSums], trial[kSums], xn[3], s[3] = {0, 0, 0}, h6[6], delta[3];
+  static_assert(NS == kSums || NS == kSumsLoss, "sixteen sums (linear) or nineteen (a robust loss)");
+  double cur[NS], trial[NS], xn[3], s[3] = {0, 0, 0}, h6[6], delta[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) x[k] = clip(x0[k], lo[k], hi[k]);
   eval(x, cur);
@@ -86,7 +151,7 @@ PAL_SOLVE_HD inline void lm_solve(const double x0[3], const double lo[3], const 
   int it = 0, stop = kStopNone;
   for (;;) {
     const double f = cur[15];
-    const double diag[3] = {cur[0], cur[3], cur[5]};
+    const double diag[3] = {cur[NS == kSums ? 0 : 16], cur[NS == kSums ? 3 : 17], cur[NS == kSums ? 5 : 18]};
     bool held[3], flat = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -126,7 +191,7 @@ PAL_SOLVE_HD inline void lm_solve(const double x0[3], const double lo[3], const 
 #pragma unroll
       for (int k = 0; k < 3; ++k) x[k] = xn[k];
 #pragma unroll
-      for (int q = 0; q < kSums; ++q) cur[q] = trial[q];
+      for (int q = 0; q < NS; ++q) cur[q] = trial[q];
       const double t = 2.0 * rho - 1.0;
       lam = fmax(lam * fmax(1.0 / 3.0, 1.0 - t * t * t), kLamMin);
       nu = 2.0;

@@ -226,9 +226,12 @@ class Engine:
         return m, ln, mics, cal, wt, ex, prm
 
     def solve_positions(self, tables, lengths, mic_positions, fs, c, calib_delays=None, weights="ones", buffer=5.0, grid=solve.GRID,
-                        max_iter=solve.MAX_ITER, extra_starts=None) -> np.ndarray:
+                        max_iter=solve.MAX_ITER, extra_starts=None, loss="linear", f_scale=1.0, return_pair_weights=False):
         """tables[B][P] (or [P]) of _ffi.RECORD, lengths[B] (or one length) -> records[B] of solve.POSITION.  ``weights``: 'ones',
-        'snr' (snr / mean(snr) of the records, as compute_weights) or an array [B][P]; ``extra_starts`` [B][n][3]."""
+        'snr' (snr / mean(snr) of the records, as compute_weights) or an array [B][P]; ``extra_starts`` [B][n][3].  ``loss``: one of
+        solve.LOSSES, with ``f_scale`` in metres of weighted residual, for tables with outlier pairs; ``return_pair_weights``:
+        -> (records, rho'(z)[B][P] at the positions: 1 for a pair the fit kept, towards 0 for one it discounted)."""
+        code, f_scale = solve.check_loss(loss, f_scale)
         tab = np.ascontiguousarray(tables, dtype=RECORD)
         if tab.ndim == 1:
             tab = tab[None]
@@ -238,20 +241,32 @@ class Engine:
         m, ln, mics, cal, wt, ex, prm = self._solve_args(b, p, lengths, mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter,
                                                          extra_starts)
         out = np.zeros(b, dtype=solve.POSITION)
-        self._check(self._lib.pal_solve_positions(self._h, tab.ctypes.data, b, m, ln.ctypes.data, mics.ctypes.data, ptr(cal), ptr(wt), ptr(ex),
-                                                  C.byref(prm), out.ctypes.data))
-        return out
+        if code == 0 and not return_pair_weights:
+            self._check(self._lib.pal_solve_positions(self._h, tab.ctypes.data, b, m, ln.ctypes.data, mics.ctypes.data, ptr(cal), ptr(wt),
+                                                      ptr(ex), C.byref(prm), out.ctypes.data))
+            return out
+        pw = np.zeros((b, p), dtype=np.float64) if return_pair_weights else None
+        self._check(self._lib.pal_solve_positions_loss(self._h, tab.ctypes.data, b, m, ln.ctypes.data, mics.ctypes.data, ptr(cal), ptr(wt),
+                                                       ptr(ex), C.byref(prm), out.ctypes.data, code, f_scale, ptr(pw)))
+        return (out, pw) if return_pair_weights else out
 
     def solve_positions_dev(self, d_tables: int, b: int, lengths, mic_positions, fs, c, calib_delays=None, weights="ones", buffer=5.0,
-                            grid=solve.GRID, max_iter=solve.MAX_ITER, extra_starts=None) -> np.ndarray:
+                            grid=solve.GRID, max_iter=solve.MAX_ITER, extra_starts=None, loss="linear", f_scale=1.0,
+                            return_pair_weights=False):
         """The same with the tables[B][P] in HBM (e.g. where gcc_phat_all_pairs_dev wrote them); returns when the records are on the host."""
+        code, f_scale = solve.check_loss(loss, f_scale)
         m = np.asarray(mic_positions).shape[0]
         m, ln, mics, cal, wt, ex, prm = self._solve_args(int(b), m * (m - 1) // 2, lengths, mic_positions, fs, c, calib_delays, weights, buffer,
                                                          grid, max_iter, extra_starts)
         out = np.zeros(int(b), dtype=solve.POSITION)
-        self._check(self._lib.pal_solve_positions_dev(self._h, C.c_void_p(d_tables), int(b), m, ln.ctypes.data, mics.ctypes.data, ptr(cal), ptr(wt),
-                                                      ptr(ex), C.byref(prm), out.ctypes.data))
-        return out
+        if code == 0 and not return_pair_weights:
+            self._check(self._lib.pal_solve_positions_dev(self._h, C.c_void_p(d_tables), int(b), m, ln.ctypes.data, mics.ctypes.data, ptr(cal),
+                                                          ptr(wt), ptr(ex), C.byref(prm), out.ctypes.data))
+            return out
+        pw = np.zeros((int(b), m * (m - 1) // 2), dtype=np.float64) if return_pair_weights else None
+        self._check(self._lib.pal_solve_positions_loss_dev(self._h, C.c_void_p(d_tables), int(b), m, ln.ctypes.data, mics.ctypes.data, ptr(cal),
+                                                           ptr(wt), ptr(ex), C.byref(prm), out.ctypes.data, code, f_scale, ptr(pw)))
+        return (out, pw) if return_pair_weights else out
 
     def phat_correlation(self, sig1, sig2) -> np.ndarray:
         a, b = f64(sig1), f64(sig2)

@@ -157,12 +157,15 @@ def host_position(table, length, mic_positions, fs, c, calib_delays, weights, cl
 
 
 def solve_positions_device(tables, lengths, mic_positions, fs, c, calib_delays=None, weights=None, buffer=5.0, grid=4, max_iter=200,
-                           extra_starts=None, engine=None, return_records=False, clustering=("kmeans", 0.001, 2)):
+                           extra_starts=None, engine=None, return_records=False, clustering=("kmeans", 0.001, 2), loss="linear",
+                           f_scale=1.0):
     """TDOA tables[B][P] (or [P]) -> positions[B][3] by the batched device solve (Engine.solve_positions; algorithm: solve.py).
     ``weights``: None / 'ones', 'snr' (the records' SNR as compute_weights weighs it) or an array [B][P].  A frame the device does
     not solve - a weight that is not finite (an infinite SNR), or no start that ended inside a stop rule - goes through the host
-    tail (solve_position) instead, as the reference would have solved it.  ``return_records``: also the solve.POSITION records."""
+    tail (solve_position) instead, as the reference would have solved it.  ``return_records``: also the solve.POSITION records.
+    ``loss`` / ``f_scale``: a robust loss of solve.LOSSES for tables with outlier pairs (the host tail knows the linear one only)."""
     from . import solve as S
+    S.check_loss(loss, f_scale)
     eng = engine or default_engine()
     tab = np.ascontiguousarray(tables, dtype=_ffi.RECORD)
     one = tab.ndim == 1
@@ -170,7 +173,8 @@ def solve_positions_device(tables, lengths, mic_positions, fs, c, calib_delays=N
         tab = tab[None]
     w = "ones" if weights is None else weights
     ln = np.broadcast_to(np.asarray(lengths, dtype=np.int64), (tab.shape[0],))
-    rec = eng.solve_positions(tab, ln, mic_positions, fs, c, calib_delays, w, buffer, grid, max_iter, extra_starts)
+    robust = {} if loss == "linear" else {"loss": loss, "f_scale": f_scale}
+    rec = eng.solve_positions(tab, ln, mic_positions, fs, c, calib_delays, w, buffer, grid, max_iter, extra_starts, **robust)
     pos = rec["position"].copy()
     for f in np.flatnonzero((rec["status"] & S.ST_CONVERGED) == 0):
         log.warning("frame %d: the device solve has no converged start (status %d), using the host solve", f, int(rec["status"][f]))
@@ -204,6 +208,11 @@ def localize_sound_source(config, calibration_data=None, audio_files=None, use_s
     solver = loc.get("solver", "host")                       # "device": the batched Levenberg-Marquardt solve (solve.py)
     if solver not in ("host", "device"):
         raise ValueError("localization.solver must be 'host' or 'device'")
+    solver_loss = {}                                         # a robust loss of the device solve (solve.LOSSES)
+    if solver == "device":
+        solver_loss = {"loss": loc.get("solver_loss", "linear"), "f_scale": loc.get("solver_f_scale", 1.0)}
+        from . import solve as S
+        S.check_loss(**solver_loss)
 
     calib_delays = None
     if calibration_data is not None:                                           # main.py:147-157
@@ -275,7 +284,7 @@ def localize_sound_source(config, calibration_data=None, audio_files=None, use_s
         else np.ones(len(mic_pairs))
     if solver == "device":
         position = solve_positions_device(table, n2, mic_positions, fs, c, calib_delays, weights,
-                                          clustering=(clustering_method, clustering_eps, clustering_min_samples))
+                                          clustering=(clustering_method, clustering_eps, clustering_min_samples), **solver_loss)
     else:
         position = solve_position(mic_positions, mic_pairs, td_diffs, c, weights, clustering_method, clustering_eps,
                                   clustering_min_samples)

@@ -49,6 +49,7 @@ import numpy as np
 ST_CONVERGED, ST_HIT_CAP, ST_BAD_WEIGHTS, ST_ON_FACE = 1, 2, 4, 8      # PAL_SOLVE_* status bits
 STOP_NONE, STOP_GRADIENT, STOP_STEP, STOP_DECREASE, STOP_DAMPING, STOP_CAP = 0, 1, 2, 3, 4, 5
 WEIGHTS = {"ones": 0, "snr": 1, "array": 2}                             # PAL_SOLVE_W_*
+LOSSES = {"linear": 0, "soft_l1": 1, "huber": 2, "cauchy": 3}           # PAL_SOLVE_LOSS_*
 
 GTOL = 1e-8
 XTOL = 1e-13
@@ -142,6 +143,66 @@ def sums(x, mics, pi, pj, b, w):
     return a6, s6, jac.T @ r, float(r @ r)
 
 
+def check_loss(loss, f_scale):
+    """-> (PAL_SOLVE_LOSS_* code, f_scale as a float); ValueError on an unknown loss or an f_scale that is not finite and positive."""
+    if not isinstance(loss, str) or loss not in LOSSES:
+        raise ValueError("loss: one of " + ", ".join(repr(k) for k in LOSSES))
+    try:
+        scale = float(f_scale)
+    except (TypeError, ValueError):
+        raise ValueError("f_scale must be a number") from None
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError("f_scale must be finite and positive")
+    return LOSSES[loss], scale
+
+
+def loss_terms(loss: str, z):
+    """rho(z), rho'(z) and rho'(z) + 2 z rho''(z) clamped at zero (Triggs' correction as SciPy applies it), written without
+    cancellation at small z like solve_math.h."""
+    z = np.asarray(z, dtype=np.float64)
+    if loss == "soft_l1":
+        t = np.sqrt(1.0 + z)
+        a = 1.0 / t
+        return 2.0 * z / (t + 1.0), a, a / (1.0 + z)
+    if loss == "huber":
+        inner = z <= 1.0
+        t = np.sqrt(np.where(inner, 1.0, z))
+        return np.where(inner, z, 2.0 * t - 1.0), np.where(inner, 1.0, 1.0 / t), np.where(inner, 1.0, 0.0)
+    if loss == "cauchy":
+        a = 1.0 / (1.0 + z)
+        return np.log1p(z), a, np.maximum((1.0 - z) * a * a, 0.0)
+    raise ValueError("loss_terms: a robust loss")
+
+
+def sums_loss(x, mics, pi, pj, b, w, loss: str, f_scale: float):
+    """The nineteen sums of a robust loss at x, z_p = r_p^2 / C^2, a_p = rho'(z_p), c_p = max(rho' + 2 z rho'', 0):
+    sum c_p j j^t, sum a_p r_p w_p (H_j - H_i), the gradient sum a_p r_p j_p, C^2 sum rho(z_p) in place of rtr, and
+    sum a_p j_k^2 (the diagonal of Marquardt's scaling and of the gradient stop rule)."""
+    diff = x - mics
+    d = np.sqrt(np.sum(diff * diff, axis=1))
+    inv = 1.0 / np.where(d > 0, d, np.inf)
+    u = diff * inv[:, None]
+    r = (d[pj] - d[pi]) * w - b
+    jac = (u[pj] - u[pi]) * w[:, None]
+    c2 = f_scale * f_scale
+    rho, a, c = loss_terms(loss, (r * r) * (1.0 / c2))
+    ar = a * r
+    ia, ib = [0, 0, 0, 1, 1, 2], [0, 1, 2, 1, 2, 2]
+    h = (np.eye(3)[ia, ib][None, :] - u[:, ia] * u[:, ib]) * inv[:, None]          # [M][6]
+    a6 = np.sum(c[:, None] * (jac[:, ia] * jac[:, ib]), axis=0)
+    s6 = np.sum((ar * w)[:, None] * (h[pj] - h[pi]), axis=0)
+    return a6, s6, jac.T @ ar, float(c2 * np.sum(rho)), np.sum(a[:, None] * (jac * jac), axis=0)
+
+
+def pair_weights(x, mics, pi, pj, b, w, loss: str, f_scale: float) -> np.ndarray:
+    """rho'(z_p) at x: how much of each pair's residual the fit kept (ones for the linear loss)."""
+    if loss == "linear":
+        return np.ones(np.asarray(b).shape[0])
+    d = np.sqrt(np.sum((x - np.asarray(mics, dtype=np.float64)) ** 2, axis=1))
+    r = (d[pj] - d[pi]) * w - b
+    return loss_terms(loss, (r * r) * (1.0 / (f_scale * f_scale)))[1]
+
+
 def held_coordinates(x, g, lower, upper) -> np.ndarray:
     return ((x <= lower) & (g > 0)) | ((x >= upper) & (g < 0))
 
@@ -185,8 +246,10 @@ def quad_form(h6, s) -> float:
                  + 2.0 * (h6[1] * s[0] * s[1] + h6[2] * s[0] * s[2] + h6[4] * s[1] * s[2]))
 
 
-def lm_solve(x0, lower, upper, mics, pi, pj, b, w, max_iter: int = MAX_ITER):
+def lm_solve(x0, lower, upper, mics, pi, pj, b, w, max_iter: int = MAX_ITER, loss: str = "linear", f_scale: float = 1.0):
     """-> (x, cost, iterations, stop rule)."""
+    if loss != "linear":
+        return lm_solve_loss(x0, lower, upper, mics, pi, pj, b, w, max_iter, loss, f_scale)
     mics = np.asarray(mics, dtype=np.float64)
     x = np.minimum(np.maximum(np.asarray(x0, dtype=np.float64), lower), upper)
     a6, s6, g, f = sums(x, mics, pi, pj, b, w)
@@ -233,9 +296,60 @@ def lm_solve(x0, lower, upper, mics, pi, pj, b, w, max_iter: int = MAX_ITER):
     return x, 0.5 * f, it, stop
 
 
+def lm_solve_loss(x0, lower, upper, mics, pi, pj, b, w, max_iter: int, loss: str, f_scale: float):
+    """lm_solve on the robust cost F = sum C^2 rho(r^2 / C^2) / 2: f is 2 F, g its gradient, the matrix sum c_p j j^t (plus the
+    second-order part where the damped free block stays positive definite), Marquardt's diagonal sum a_p j_k^2."""
+    mics = np.asarray(mics, dtype=np.float64)
+    x = np.minimum(np.maximum(np.asarray(x0, dtype=np.float64), lower), upper)
+    a6, s6, g, f, diag = sums_loss(x, mics, pi, pj, b, w, loss, f_scale)
+    lam, nu, it = LAM0, 2.0, 0
+    while True:
+        held = held_coordinates(x, g, lower, upper)
+        if np.all(held | (np.abs(g) <= GTOL * np.sqrt(diag * f))):
+            stop = STOP_GRADIENT
+            break
+        if it >= max_iter:
+            stop = STOP_CAP
+            break
+        it += 1
+        h6 = a6 + s6
+        ok, delta = damped_step(h6, diag, g, lam, held)
+        if not ok:
+            h6 = a6
+            ok, delta = damped_step(h6, diag, g, lam, held)
+        if ok:
+            xn = np.minimum(np.maximum(x + delta, lower), upper)
+            s = xn - x
+            if np.max(np.abs(s)) <= XTOL * (XTOL + np.max(np.abs(x))):
+                stop = STOP_STEP
+                break
+            an, sn, gn, fn, dn = sums_loss(xn, mics, pi, pj, b, w, loss, f_scale)
+        if ok and fn < f:
+            pred = -(2.0 * float(g @ s) + quad_form(h6, s))
+            rho = (f - fn) / pred if pred > 0 else 1.0
+            small = (f - fn) <= FTOL * f and lam <= 1.0
+            x, a6, s6, g, f, diag = xn, an, sn, gn, fn, dn
+            t = 2.0 * rho - 1.0
+            lam = max(lam * max(1.0 / 3.0, 1.0 - t * t * t), LAM_MIN)
+            nu = 2.0
+            if small:
+                stop = STOP_DECREASE
+                break
+        else:
+            lam = lam * nu
+            nu = 2.0 * nu
+            if lam > LAM_MAX:
+                stop = STOP_DAMPING
+                break
+    return x, 0.5 * f, it, stop
+
+
 def solve_frame(k_sel, length: int, mics, fs: float, c: float, calib=None, weights="ones", snr=None, buffer: float = 5.0,
-                grid: int = GRID, max_iter: int = MAX_ITER, extra_starts=None, return_starts: bool = False):
-    """One frame -> a POSITION record (``weights``: 'ones', 'snr' (needs ``snr``), or an array of P weights)."""
+                grid: int = GRID, max_iter: int = MAX_ITER, extra_starts=None, return_starts: bool = False,
+                loss: str = "linear", f_scale: float = 1.0):
+    """One frame -> a POSITION record (``weights``: 'ones', 'snr' (needs ``snr``), or an array of P weights; ``loss``: one of
+    LOSSES with scale ``f_scale``, in metres of weighted residual)."""
+    _, f_scale = check_loss(loss, f_scale)
     mics = np.asarray(mics, dtype=np.float64)
     m = mics.shape[0]
     pi, pj = pair_indices(m)
@@ -259,7 +373,10 @@ def solve_frame(k_sel, length: int, mics, fs: float, c: float, calib=None, weigh
         return (rec, None, None) if return_starts else rec
     b = (c * td) * w
     starts = start_points(mics, lower, upper, grid, extra_starts)
-    results = [lm_solve(s, lower, upper, mics, pi, pj, b, w, max_iter) for s in starts]
+    if loss == "linear":
+        results = [lm_solve(s, lower, upper, mics, pi, pj, b, w, max_iter) for s in starts]
+    else:
+        results = [lm_solve_loss(s, lower, upper, mics, pi, pj, b, w, max_iter, loss, f_scale) for s in starts]
     best, best_capped, nconv = -1, -1, 0
     for k, (_, cost, _, stop) in enumerate(results):
         if stop != STOP_CAP:

@@ -38,17 +38,28 @@ def position_stream(bases: Sequence[np.ndarray], delays: Sequence[np.ndarray], g
                     totals: Sequence[int], trim_len: int, mic_positions, c: float, filter_method: str = "butterworth",
                     max_expected_delay: Optional[float] = None, engine: Optional[Engine] = None, frames_per_batch: int = 128,
                     timings: Optional[Dict[str, float]] = None, calib_delays=None, weights: str = "ones", buffer: float = 5.0,
-                    grid: int = solve.GRID, max_iter: int = solve.MAX_ITER) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                    grid: int = solve.GRID, max_iter: int = solve.MAX_ITER, loss: str = "linear",
+                    f_scale: float = 1.0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """The chain of tdoa_stream with the position solve (solve.py) run on the table buffer while it is still in HBM:
     -> (positions[F] of solve.POSITION records, tables[F][P], lengths[F]).  Tables and lengths are tdoa_stream's; the positions are
-    what Engine.solve_positions returns for those tables (``weights``: 'ones' or 'snr').  A frame without the converged bit in
-    ``positions["status"]`` is the caller's to hand to main.solve_positions_device / solve_position."""
-    if weights not in ("ones", "snr"):
-        raise ValueError("weights: 'ones' or 'snr'")
-    args = dict(mic_positions=mic_positions, fs=fs, c=c, calib_delays=calib_delays, weights=weights, buffer=buffer, grid=grid, max_iter=max_iter)
+    what Engine.solve_positions returns for those tables (``weights``: 'ones' or 'snr'; ``loss`` / ``f_scale``: a robust loss for
+    tables with outlier pairs).  A frame without the converged bit in ``positions["status"]`` is the caller's to hand to
+    main.solve_positions_device / solve_position."""
+    args = _solve_keywords(mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter, loss, f_scale)
     tables, lengths, positions = _chain(bases, delays, gains, fs, totals, trim_len, filter_method, max_expected_delay, engine,
                                         frames_per_batch, timings, args)
     return positions, tables, lengths
+
+
+def _solve_keywords(mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter, loss, f_scale):
+    """Keywords of Engine.solve_positions_dev for a stream, checked before any GPU work; the linear loss passes none of its own."""
+    if weights not in ("ones", "snr"):
+        raise ValueError("weights: 'ones' or 'snr'")
+    solve.check_loss(loss, f_scale)
+    args = dict(mic_positions=mic_positions, fs=fs, c=c, calib_delays=calib_delays, weights=weights, buffer=buffer, grid=grid, max_iter=max_iter)
+    if loss != "linear":
+        args.update(loss=loss, f_scale=f_scale)
+    return args
 
 
 def _laps(eng, timings):
@@ -314,12 +325,11 @@ def recorded_position_stream(recordings, fs_in: float, fs: float, frame_len: int
                              filter_method: str = "butterworth", max_expected_delay: Optional[float] = None,
                              engine: Optional[Engine] = None, frames_per_batch: int = 128, timings: Optional[Dict[str, float]] = None,
                              calib_delays=None, weights: str = "ones", buffer: float = 5.0, grid: int = solve.GRID,
-                             max_iter: int = solve.MAX_ITER) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                             max_iter: int = solve.MAX_ITER, loss: str = "linear",
+                             f_scale: float = 1.0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """recorded_tdoa_stream with the position solve of position_stream on each batch's tables while they are in HBM:
     -> (positions[F] of solve.POSITION records, tables[F][P], lengths[F])."""
-    if weights not in ("ones", "snr"):
-        raise ValueError("weights: 'ones' or 'snr'")
-    args = dict(mic_positions=mic_positions, fs=fs, c=c, calib_delays=calib_delays, weights=weights, buffer=buffer, grid=grid, max_iter=max_iter)
+    args = _solve_keywords(mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter, loss, f_scale)
     tables, lengths, positions = _recorded(recordings, fs_in, fs, frame_len, hop, filter_method, max_expected_delay, engine,
                                            frames_per_batch, timings, args)
     return positions, tables, lengths

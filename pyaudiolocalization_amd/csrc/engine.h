@@ -128,6 +128,7 @@ struct Engine {
   bool allow_rader = true;         // PAL_RADER=0 keeps the row pass on the in-LDS chirp convolution
   int four_reg = -1;               // PAL_FOUR_REG: register-resident rows of the four-step route: -1 choose, 12 / 13 force 2^12 / 2^13, 0 = LDS tiles only
   bool xcd_rows = true;            // PAL_XCD_ROWS=0: row passes in plain workgroup order (pfa_kernels.h: row_work_item)
+  bool rows_shared = true;         // PAL_ROWS_SHARED=0: the Rader row pass reads all four spectrum rows even when two are the same (pfa_rader.h)
   bool allow_big = true;           // PAL_PFA_BIG=0: no register-resident row tiles (N2 <= 2048 only, as in round 1)
   std::string err;
   static constexpr int kDefaultChunk = 128;

@@ -305,6 +305,8 @@ int pal_create(int device, pal_handle* out) {
   if (env) e->four_reg = atoi(env);
   env = getenv("PAL_XCD_ROWS");
   if (env) e->xcd_rows = atoi(env) != 0;
+  env = getenv("PAL_ROWS_SHARED");
+  if (env) e->rows_shared = atoi(env) != 0;
   env = getenv("PAL_PFA_FWD");
   if (env) e->pfa_forward = atoi(env) != 0;
   env = getenv("PAL_FUSED");

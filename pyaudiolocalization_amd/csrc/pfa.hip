@@ -255,7 +255,7 @@ int Engine::pfa_rows(const Plan& pl, const cd* permuted, const int4* quads, int 
   if (f.rader) {
     ProfScope ps(this, "k_pfa_rows_rader<11,9,10>", on);
     PfaRaderArgs a{permuted, quads, Y, f.rd_bhat, f.r1, f.rd_ridx, f.rowtab,
-                   f.n1, f.n2, f.rows(), G, 1.0f / float(f.n1), 1.0 / double(pl.n), nullptr, xcd_rows};
+                   f.n1, f.n2, f.rows(), G, 1.0f / float(f.n1), 1.0 / double(pl.n), nullptr, xcd_rows, rows_shared};
     k_pfa_rows_rader<11, 9, 10><<<dim3(row_work_grid(G, f.rows(), xcd_rows)), dim3(256), 0, on>>>(a);
     PAL_HIP(hipGetLastError());
   } else if (f.lm >= 13) {

@@ -18,6 +18,8 @@
 //   inverse    9-axis, 11-axis; C[s] lands at pos(s)
 //   epilogue   four bins per lane: X[e] = x[0] + C[log_g e] through a position table, column twiddle, coalesced stores
 #pragma once
+#include <type_traits>
+
 #include "conv_kernels.h"
 #include "mixed_radix.h"
 #include "pfa_kernels.h"   // swap_pair
@@ -37,6 +39,7 @@ struct PfaRaderArgs {
   double scale;          // 1 / n: the x[0] and sum terms bypass the scaled convolution
   unsigned long long* stamps;   // diagnostics only (tools/microbench_pfa): 100 MHz clock reads of lane 0 per phase
   int xcd;               // 1: XCD-aware order of the workgroups (row_work_item, pfa_kernels.h)
+  int shared;            // 1: a transform whose two pairs share their first microphone (a == c) reads that row once
 };
 
 // One stage along axis R1 of both tiles: 2 L / R1 = 180 butterflies on the first three wavefronts (the fourth has none)
@@ -125,43 +128,63 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
   const int4 q = make_int4(qp[0], qp[1], qp[2], qp[3]);
   const size_t mic = size_t(a.NR) * N2, off = size_t(k1) * N2;
   const bool second = q.z >= 0;
+  // consecutive pairs of the row-major i < j list are (i, j), (i, j + 1): most transforms have a == c
+  const bool shared = a.shared && second && q.x == q.z;       // (workgroup-uniform)
   const cd* sa = a.SP + size_t(q.x) * mic + off;
   const cd* sb = a.SP + size_t(q.y) * mic + off;
   const cd* sc = second ? a.SP + size_t(q.z) * mic + off : sa;
   const cd* sd = second ? a.SP + size_t(q.w) * mic + off : sb;
-  const double keep2 = second ? 1.0 : 0.0;
+  double keep2 = second ? 1.0 : 0.0;
+  // Opaque: the shared body implies keep2 = 1, and a compiler that saw it would drop the product and contract the
+  // whitening's last multiplication into the sums below - one rounding fewer than the four-row body, records off by an ulp.
+  asm volatile("" : "+s"(keep2));
   // tile 0: R^p + i R^q at (k1, e);  tile 1: conj(R^p) + i conj(R^q) = the reversed row N1 - k1, held at the SAME
   // positions (it is transformed as the reversed sequence and its outputs are stored reversed)
   constexpr int NB1 = L / R1, HR = (R1 + 1) / 2;              // 90 butterflies per tile, 6 inputs per half-wavefront
   static_assert(NB1 <= 96 && 2 * HR >= R1, "three wavefronts of 32 butterfly pairs");
-  if (tid < 192) {                                            // (wave-uniform)
-    const int upper = (tid >> 5) & 1, bf = 32 * (tid >> 6) + (tid & 31);
-    const int bfc = bf < NB1 ? bf : NB1 - 1;
-    cd va[HR], vb[HR], vc[HR], vd[HR];
+  // SH: the second pair's first row IS the first pair's (sc == sa, a second pair exists): 18 requests per lane instead
+  // of 24 and no vc[]; the values and the expressions behind them are the same
+  const auto first_stage = [&](auto sh) {
+    constexpr bool SH = decltype(sh)::value;
+    if (tid < 192) {                                          // (wave-uniform)
+      const int upper = (tid >> 5) & 1, bf = 32 * (tid >> 6) + (tid & 31);
+      const int bfc = bf < NB1 ? bf : NB1 - 1;
+      cd va[HR], vb[HR], vc[SH ? 1 : HR], vd[HR];
 #pragma unroll
-    for (int u = 0; u < HR; ++u) {
-      const int j = upper * HR + u;
-      const int at = bfc + NB1 * (j < R1 ? j : R1 - 1);
-      va[u] = sa[at]; vb[u] = sb[at]; vc[u] = sc[at]; vd[u] = sd[at];
-    }
-    cd v[2 * HR];
+      for (int u = 0; u < HR; ++u) {
+        const int j = upper * HR + u;
+        const int at = bfc + NB1 * (j < R1 ? j : R1 - 1);
+        va[u] = sa[at]; vb[u] = sb[at];
+        if constexpr (!SH) vc[u] = sc[at];
+        vd[u] = sd[at];
+      }
+      if constexpr (SH) __builtin_amdgcn_sched_barrier(0);    // all 18 requests in flight before the first wait
+      cd v[2 * HR];
 #pragma unroll
-    for (int u = 0; u < HR; ++u) {
-      const cd r1 = whiten(va[u], vb[u]);
-      const cd r2 = cscale(whiten(vc[u], vd[u]), keep2);
+      for (int u = 0; u < HR; ++u) {
+        const cd r1 = whiten(va[u], vb[u]);
+        cd r2;
+        if constexpr (SH) r2 = cscale(whiten(va[u], vd[u]), keep2);
+        else r2 = cscale(whiten(vc[u], vd[u]), keep2);
+        const cd x = mk(r1.x - r2.y, r1.y + r2.x), z = mk(r1.x + r2.y, r2.x - r1.y);
+        // lower half: v[u] = own x, v[HR + u] = the upper half's x;  upper half: v[u] = the lower half's z, v[HR + u] = own z
+        swap_pair(x.x, z.x, v[u].x, v[HR + u].x);
+        swap_pair(x.y, z.y, v[u].y, v[HR + u].y);
+      }
+      dft_sym<R1, false>(v);
+      if (bf < NB1) axis_store<R1>(tile, upper, Axes<R1, R2, R3>::base1(bf), Axes<R1, R2, R3>::kStride1, v);   // in place
+    } else if (tid == 192) {                                  // bin 0 (the row's last position) bypasses the convolution
+      const cd s0 = sa[L];
+      const cd r1 = whiten(s0, sb[L]);
+      cd r2;
+      if constexpr (SH) r2 = cscale(whiten(s0, sd[L]), keep2);
+      else r2 = cscale(whiten(sc[L], sd[L]), keep2);
       const cd x = mk(r1.x - r2.y, r1.y + r2.x), z = mk(r1.x + r2.y, r2.x - r1.y);
-      // lower half: v[u] = own x, v[HR + u] = the upper half's x;  upper half: v[u] = the lower half's z, v[HR + u] = own z
-      swap_pair(x.x, z.x, v[u].x, v[HR + u].x);
-      swap_pair(x.y, z.y, v[u].y, v[HR + u].y);
+      dc[0] = x; dc[1] = z;
     }
-    dft_sym<R1, false>(v);
-    if (bf < NB1) axis_store<R1>(tile, upper, Axes<R1, R2, R3>::base1(bf), Axes<R1, R2, R3>::kStride1, v);   // in place
-  } else if (tid == 192) {                                    // bin 0 (the row's last position) bypasses the convolution
-    const cd r1 = whiten(sa[L], sb[L]);
-    const cd r2 = cscale(whiten(sc[L], sd[L]), keep2);
-    const cd x = mk(r1.x - r2.y, r1.y + r2.x), z = mk(r1.x + r2.y, r2.x - r1.y);
-    dc[0] = x; dc[1] = z;
-  }
+  };
+  if (shared) first_stage(std::true_type{});
+  else first_stage(std::false_type{});
   __syncthreads();
   stamp();
 

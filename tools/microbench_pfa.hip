@@ -1,6 +1,7 @@
 // Ablation timings of the prime-factor kernels on the metric geometry (n = 88199 = 89 x 991, G transforms).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -fno-signed-zeros -I pyaudiolocalization_amd/csrc -I include \
 //         tools/microbench_pfa.hip -o tools/microbench_pfa
+//   tools/microbench_pfa [G [rows]]: G transforms per launch (128); a second argument stops after the row passes
 // Random data (the timing does not depend on values); not part of the product or the tests.
 #include <hip/hip_runtime.h>
 
@@ -387,23 +388,30 @@ int main(int argc, char** argv) {
     for (cd* p : {bhat, t2f, t2i, t3f, t3i}) CHECK(hipMemcpy(p, rnd.data(), sizeof(cd) * 1024, hipMemcpyHostToDevice));
     unsigned long long* st;
     CHECK(hipMalloc(&st, sizeof(unsigned long long) * 8 * grid));
-    PfaRaderArgs ra{SP, quad, Y, bhat, r1, ridx, rowtab, N1, N2, NR, G, 1.0f / float(N1), 1.0 / double(n), nullptr};
-    time_it("rows (Rader 11 x 9 x 10): product", 20, [&] { k_pfa_rows_rader<11, 9, 10><<<dim3(grid), dim3(256)>>>(ra); });
+    PfaRaderArgs ra{SP, quad, Y, bhat, r1, ridx, rowtab, N1, N2, NR, G, 1.0f / float(N1), 1.0 / double(n), nullptr, 0, 1};
     ra_keep = ra;
-    ra.stamps = st;
-    k_pfa_rows_rader<11, 9, 10><<<dim3(grid), dim3(256)>>>(ra);
-    CHECK(hipDeviceSynchronize());
-    std::vector<unsigned long long> hs(size_t(8) * grid);
-    CHECK(hipMemcpy(hs.data(), st, hs.size() * 8, hipMemcpyDeviceToHost));
-    const char* names[4] = {"loads + whiten + radix 11", "radix 9, seam, inverse 9 / 11", "epilogue", "total"};
-    for (int ph = 0; ph < 4; ++ph) {
-      std::vector<double> d(grid);
-      for (unsigned w = 0; w < grid; ++w)
-        d[w] = ph < 3 ? double(hs[size_t(w) * 8 + ph + 1] - hs[size_t(w) * 8 + ph]) / 100.0 : double(hs[size_t(w) * 8 + 3] - hs[size_t(w) * 8]) / 100.0;
-      std::sort(d.begin(), d.end());
-      printf("  rader phase %-26s median %6.2f us  p90 %6.2f us\n", names[ph], d[grid / 2], d[grid * 9 / 10]);
+    // every transform of `quad` has a == c: `shared` = 1 reads that row once (18 requests per lane), 0 keeps the four-row body (24)
+    for (int sh : {1, 0, 1, 0}) {
+      ra.shared = sh;
+      ra.stamps = nullptr;
+      time_it(sh ? "rows (Rader 11 x 9 x 10): product" : "rows (Rader 11 x 9 x 10): four-row first stage", 20,
+              [&] { k_pfa_rows_rader<11, 9, 10><<<dim3(grid), dim3(256)>>>(ra); });
+      ra.stamps = st;
+      k_pfa_rows_rader<11, 9, 10><<<dim3(grid), dim3(256)>>>(ra);
+      CHECK(hipDeviceSynchronize());
+      std::vector<unsigned long long> hs(size_t(8) * grid);
+      CHECK(hipMemcpy(hs.data(), st, hs.size() * 8, hipMemcpyDeviceToHost));
+      const char* names[4] = {"loads + whiten + radix 11", "radix 9, seam, inverse 9 / 11", "epilogue", "total"};
+      for (int ph = 0; ph < 4; ++ph) {
+        std::vector<double> d(grid);
+        for (unsigned w = 0; w < grid; ++w)
+          d[w] = ph < 3 ? double(hs[size_t(w) * 8 + ph + 1] - hs[size_t(w) * 8 + ph]) / 100.0 : double(hs[size_t(w) * 8 + 3] - hs[size_t(w) * 8]) / 100.0;
+        std::sort(d.begin(), d.end());
+        printf("  rader phase %-26s median %6.2f us  p90 %6.2f us\n", names[ph], d[grid / 2], d[grid * 9 / 10]);
+      }
     }
   }
+  if (argc > 2) return 0;   // any second argument: the row passes only
   const dim3 cg(unsigned(G) * nblk, 1);
   time_it("cols: product", 20, [&] { k_pfa_cols<kPfaTC, kPfaUnr><<<cg, dim3(256)>>>(Y, corr, stride, N1, N2, G, 4, T, nullptr); });
   time_it("cols: product with 3 steps per batch", 20, [&] { k_pfa_cols<kPfaTC, 3><<<cg, dim3(256)>>>(Y, corr, stride, N1, N2, G, 4, T, nullptr); });

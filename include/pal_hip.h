@@ -116,7 +116,11 @@ int pal_gcc_phat_all_pairs_dev(pal_handle h, const double* d_frames, int B, int 
 /* Non-finite samples: the reference confines a NaN to the pairs of its own microphone.  Here two pairs share one complex
  * transform, so a frame with a NaN or an infinity makes the batched calls (all_pairs, pairs) fail with PAL_ERR_INVALID
  * (reported by the call itself, or by pal_synchronize for the _dev forms) instead of returning rows that differ from the
- * reference's.  The single-pair entry points below have no partner pair and behave like the reference. */
+ * reference's.  The single-pair entry points below have no partner pair and behave like the reference.
+ * Amplitude: wherever two real rows share one complex transform (the forward spectra of the batched PHAT calls, xcorr /
+ * sync_measure, fractional_delay, simulate_multipath) each row goes in scaled by an exact power of two to [1, 2) and comes
+ * out scaled back, so a row's error is relative to its own max |x| and does not depend on its partner's amplitude (zero
+ * rows and rows whose maximum is subnormal keep scale 1). */
 
 /* explicit pair list over rows[R][L]: pairs[P][2] row indices -> table[P].  Carries the 1000 shuffled
  * correlations per pair of bootstrap_significance (utils.py:183-216) as one call (rows = sig1 + shuffles of sig2,

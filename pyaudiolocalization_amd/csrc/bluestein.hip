@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "conv_kernels.h"
+#include "reduce.h"
 
 namespace pal {
 
@@ -180,19 +181,25 @@ struct CorrStorer {
 // The same pass looks for non-finite samples.  The reference confines a NaN to the pairs of its own microphone; here the
 // pair packed into the same complex transform would be poisoned as well, so a non-finite frame sets kStInputNonFinite in the
 // engine's status word kStInput and the call is reported as PAL_ERR_INVALID by pal_synchronize (never silently wrong rows).
+// The flag of a live row also carries its power-of-two exponent (reduce.h: kRowExpBias + ilogb(max |x|)): the packed forward
+// transform (pfa_forward.h) scales both of its frames to [1, 2) with it, so a quiet frame does not drown in a loud partner.
 __global__ __launch_bounds__(256) void k_row_nonzero(const double* __restrict__ frames, size_t frame_stride, int len, int* __restrict__ flags,
                                                      int* __restrict__ status) {
   const double* x = frames + size_t(blockIdx.x) * frame_stride;
+  __shared__ double rd[4];
   bool any = false, bad = false;
+  double top = 0.0;
   for (int i = threadIdx.x; i < len; i += 256) {
     const double v = x[i];
     any = any || v != 0.0;
     bad = bad || !(v - v == 0.0);                             // NaN or infinity
+    top = fmax(top, fabs(v));
   }
   const int all = __syncthreads_or(any ? 1 : 0);
   const int nonfinite = __syncthreads_or(bad ? 1 : 0);
+  top = block_max(top, rd, threadIdx.x);
   if (threadIdx.x == 0) {
-    flags[blockIdx.x] = all;
+    flags[blockIdx.x] = all ? kRowExpBias + (nonfinite ? 0 : row_exponent(top)) : 0;
     if (nonfinite && status) atomicOr(status + kStInput, kStInputNonFinite);
   }
 }
@@ -477,7 +484,7 @@ int Engine::forward_spectra(Plan& pl, const double* frames, size_t frame_stride,
     k_row_nonzero<<<dim3(rows), dim3(256), 0, stream>>>(frames, frame_stride, len, nonzero, status);
     PAL_HIP(hipGetLastError());
   }
-  if (pfa_forward_applies(pl, len)) return pfa_forward_spectra(pl, frames, frame_stride, rows, len, spectra);
+  if (pfa_forward_applies(pl, len)) return pfa_forward_spectra(pl, frames, frame_stride, rows, len, spectra, nonzero);
   const Conv& c = pl.fwd;
   cd* W = nullptr;
   PAL_TRY(scratch(kWsWork, size_t(chunk) * c.M() * sizeof(cd), &W));

@@ -253,7 +253,7 @@ struct Engine {
   int pfa_pair_group_fused(const Plan& pl, const cd* permuted, const int4* quads, int G, int rows, cd* Y, double* corr, size_t stride,
                            const int* zero_rows, const pal_phat_params& prm, int n2, pal_pair_record* table, int32_t* ksel_multi, int slot);
   bool pfa_forward_applies(const Plan& pl, int len) const;
-  int pfa_forward_spectra(Plan& pl, const double* frames, size_t frame_stride, int rows, int len, cd* spectra);
+  int pfa_forward_spectra(Plan& pl, const double* frames, size_t frame_stride, int rows, int len, cd* spectra, const int* flags);
   bool pfa_forward = true;    // PAL_PFA_FWD=0: forward spectra on the four-step route even where the prime-factor cut applies
   bool fin_cols = true;       // PAL_FIN=0: the fused column pass always stores the correlation rows for a finish launch (pfa_cols_stats.h) instead
                               // of finishing the rows itself without storing them (pfa_cols_fin.h: one peak per row, nobody asks for `corr`)

@@ -301,7 +301,8 @@ bool Engine::pfa_forward_applies(const Plan& pl, int len) const {
   return pfa_forward && f.on() && f.rader && f.nch >= 1 && (len - 1) / f.n2 <= (f.n1 - 1) / 2;
 }
 
-int Engine::pfa_forward_spectra(Plan& pl, const double* frames, size_t frame_stride, int rows, int len, cd* spectra) {
+// `flags` (optional): the flag words k_row_nonzero wrote for these frames; they carry the exponents of the row rescale.
+int Engine::pfa_forward_spectra(Plan& pl, const double* frames, size_t frame_stride, int rows, int len, cd* spectra, const int* flags) {
   const Pfa& f = pl.pfa;
   cd* Y = nullptr;
   PAL_TRY(scratch(kWsWork, size_t(chunk) * size_t(pl.n) * sizeof(cd), &Y));
@@ -310,7 +311,8 @@ int Engine::pfa_forward_spectra(Plan& pl, const double* frames, size_t frame_str
     const int G = (R + 1) / 2;
     {
       ProfScope ps(this, "k_pfa_fwd_cols", stream);
-      const PfaFwdColsArgs a{frames + size_t(r0) * frame_stride, frame_stride, len, R, Y, f.T, f.n1, f.n2, G, f.nch};
+      const PfaFwdColsArgs a{frames + size_t(r0) * frame_stride, frame_stride, len, R, Y, f.T, f.n1, f.n2, G, f.nch,
+                             flags ? flags + r0 : nullptr};
       const unsigned nblk = unsigned(f.n2 + 63) / 64;
       k_pfa_fwd_cols<kPfaTC, kPfaUnr><<<dim3(unsigned(G) * nblk, unsigned(f.nch + 3) / 4), dim3(256), 0, stream>>>(a);
       PAL_HIP(hipGetLastError());
@@ -318,7 +320,7 @@ int Engine::pfa_forward_spectra(Plan& pl, const double* frames, size_t frame_str
     {
       ProfScope ps(this, "k_pfa_fwd_rows_rader<11,9,10>", stream);
       const PfaFwdRowsArgs a{Y, spectra + size_t(r0) * pl.spec_stride(), f.rd_bhat_f, f.r1,
-                             f.rd_qidx, f.rowtab, f.n1, f.n2, f.rows(), G, R, 1.0f / float(f.n1)};
+                             f.rd_qidx, f.rowtab, f.n1, f.n2, f.rows(), G, R, 1.0f / float(f.n1), flags ? flags + r0 : nullptr};
       k_pfa_fwd_rows_rader<11, 9, 10><<<dim3(unsigned(G) * unsigned(f.rows())), dim3(256), 0, stream>>>(a);
       PAL_HIP(hipGetLastError());
     }

@@ -10,10 +10,15 @@
 // way out, X_a[k] = (Z[k] + conj Z[n - k]) / 2, X_b[k] = (Z[k] - conj Z[n - k]) / 2i, writing SP[mic][k1][.] in the
 // generator order the inverse's row pass reads (position s holds bin k2 = g^-s, bin 0 last).
 //
+// The two frames of a transform are scaled to [1, 2) by exact powers of two (`flags`: the words of k_row_nonzero, reduce.h):
+// the column pass multiplies the samples by 2^-e_a / 2^-e_b, the row pass multiplies X_a / X_b back after separating them,
+// so the whitening's 1e-10 sees the true |R| and the rounding error of a loud frame does not land in a quiet partner.
+//
 // Replaces, for plans with Rader rows, the four-step chirp convolution of the forward transform (bluestein.hip:
 // one real frame per 196608-point transform, three passes over the workspace): numpy.fft.fft(sig, n) of utils.py:114-115.
 #pragma once
 #include "pfa_rader.h"
+#include "reduce.h"
 
 namespace pal {
 
@@ -24,6 +29,7 @@ struct PfaFwdColsArgs {
   cd* Y;                 // [G][N1][N2]: column DFTs A[k1][m2] of the packed frames
   const double* T;       // cos / sin table of the inverse's column pass (symmetric in its two indices)
   int N1, N2, G, nch;
+  const int* flags;      // [rows] flag words of the frames (exponents), or null: no scaling
 };
 
 // grid = (G * ceil(N2 / 64), ceil(nch / 4)); one lane per column m2, the wavefronts take chunks of TC output rows k1
@@ -51,6 +57,8 @@ __global__ __launch_bounds__(256) void k_pfa_fwd_cols(PfaFwdColsArgs a) {
 #pragma unroll
   for (int tt = 0; tt < TC; ++tt) ac[tt] = as[tt] = bc[tt] = bs[tt] = 0.0;
   double suma = 0.0, sumb = 0.0;
+  const double sa = a.flags ? ldexp(1.0, -flag_exponent(a.flags[2 * g])) : 1.0;                       // 2^-e_a, 2^-e_b
+  const double sb = a.flags && second ? ldexp(1.0, -flag_exponent(a.flags[2 * g + 1])) : 1.0;
   const double ra0 = xa[at(0)], rb0 = xb[at(0)];
   const double* Tj = a.T + size_t(ch) * 2 * TC;
   const size_t tstep = size_t(a.nch) * 2 * TC;
@@ -61,7 +69,7 @@ __global__ __launch_bounds__(256) void k_pfa_fwd_cols(PfaFwdColsArgs a) {
     va[u] = xa[at(t)];
     vb[u] = xb[at(t)];
   }
-  const double a0 = inside(0) ? ra0 : 0.0, b0 = second && inside(0) ? rb0 : 0.0;
+  const double a0 = inside(0) ? ra0 * sa : 0.0, b0 = second && inside(0) ? rb0 * sb : 0.0;
   for (int t = 1; t <= h; t += UNR) {
     double na[UNR], nb[UNR];
 #pragma unroll
@@ -73,7 +81,7 @@ __global__ __launch_bounds__(256) void k_pfa_fwd_cols(PfaFwdColsArgs a) {
 #pragma unroll
     for (int u = 0; u < UNR; ++u, Tj += tstep) {              // steps beyond h meet zero rows of the table
       const bool in = t + u <= h && inside(t + u);
-      const double av = in ? va[u] : 0.0, bv = in && second ? vb[u] : 0.0;
+      const double av = in ? va[u] * sa : 0.0, bv = in && second ? vb[u] * sb : 0.0;
       suma += av;
       sumb += bv;
 #pragma unroll
@@ -110,6 +118,7 @@ struct PfaFwdRowsArgs {
   const int2* rowtab;    // per row of Y: (u1 row mod N1, -)
   int N1, N2, NR, G, rows;
   float inv;             // 1 / N1
+  const int* flags;      // as PfaFwdColsArgs::flags: the spectra are multiplied back by 2^e_a / 2^e_b
 };
 
 // grid = G * NR workgroups of 256 lanes: rows k1 (tile 0) and N1 - k1 (tile 1) of one packed transform.
@@ -170,6 +179,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
   const size_t mic = size_t(a.NR) * N2;
   cd* Sa = a.SP + size_t(2 * g) * mic + size_t(k1) * N2;
   cd* Sb = Sa + mic;
+  const double ua = a.flags ? 0.5 * ldexp(1.0, flag_exponent(a.flags[2 * g])) : 0.5;                  // 2^e_a / 2, 2^e_b / 2
+  const double ub = a.flags && second ? 0.5 * ldexp(1.0, flag_exponent(a.flags[2 * g + 1])) : 0.5;
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int p = tid + 256 * u;
@@ -187,8 +198,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
         Z0 = sum0;
         Z1 = sum1;
       }
-      Sa[p] = mk(0.5 * (Z0.x + Z1.x), 0.5 * (Z0.y - Z1.y));   // (Z + conj Z') / 2
-      if (second) Sb[p] = mk(0.5 * (Z0.y + Z1.y), 0.5 * (Z1.x - Z0.x));   // (Z - conj Z') / 2i
+      Sa[p] = mk(ua * (Z0.x + Z1.x), ua * (Z0.y - Z1.y));     // (Z + conj Z') / 2
+      if (second) Sb[p] = mk(ub * (Z0.y + Z1.y), ub * (Z1.x - Z0.x));     // (Z - conj Z') / 2i
     }
   }
 }

@@ -27,6 +27,15 @@ template <int NW = 4> __device__ inline double block_max(double v, double* rd, i
   return r;
 }
 
+// Two real rows share one complex transform in several places (pfa_forward.h, sim.hip), and the rounding error of the louder
+// half, 2^-53 |loud|, lands in the quieter half.  Each row is therefore scaled by 2^-e on the way in and by 2^e on the way out,
+// e = ilogb(max |x|) of the row: exact, so a row's result no longer depends on its partner's amplitude, and rows of equal
+// exponent give the bits they gave unscaled.  Zero rows, non-finite maxima and subnormal maxima keep e = 0.
+__device__ __forceinline__ int row_exponent(double top) { return top >= 2.2250738585072014e-308 && isfinite(top) ? ilogb(top) : 0; }
+// the flag word of a frame row (k_row_nonzero): 0 = silent row, else kRowExpBias + e
+constexpr int kRowExpBias = 2048;
+__device__ __forceinline__ int flag_exponent(int flag) { return flag ? flag - kRowExpBias : 0; }
+
 // arg-best over (value, index); index < 0 marks "no entry".
 //   MODE 0: max value, lowest index on ties (np.argmax)   MODE 1: min value, lowest index on ties
 //   MODE 2: max value, highest index on ties (peak priority)

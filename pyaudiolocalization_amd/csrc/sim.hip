@@ -31,10 +31,13 @@ struct SimLoader {
   int K, rows, rows_per_base, N, row0;   // row0: first row of this launch group
   double val;             // 1.0 / (2N * (1/fs)): numpy.fft.fftfreq spacing (signal_processing.py:70)
   const cd* w;
+  const int* base_exp;    // [bases] exponent of each base signal (k_row_exponent): its spectrum goes in times 2^-e
   __device__ cd term(int r, unsigned kk, double f, bool nyquist, bool mirror) const {
     r += row0;
     if (r >= rows) return mk(0, 0);
-    const cd x = X[size_t(r / rows_per_base) * (N + 1) + kk];
+    const int base = r / rows_per_base;
+    cd x = X[size_t(base) * (N + 1) + kk];
+    x = mk(ldexp(x.x, -base_exp[base]), ldexp(x.y, -base_exp[base]));
     double hx = 0, hy = 0;
     const double a = -6.283185307179586 * f;               // (-1j * 2 * np.pi * freqs) ...
     for (int p = 0; p < K; ++p) {
@@ -68,6 +71,8 @@ struct SimStorer {
   int rows, N, out_len, fl, row0;
   double step_in, step_out;   // 1/(fl-1), -1/(fl-1)  (np.linspace steps, signal_processing.py:77-78)
   const cd* w;
+  const int* unexp;           // exponent of the base of row r (k_row_exponent), or null where the rows are normalised afterwards
+  int rows_per_base;
   __device__ double fade(int j) const {
     if (j < fl) return fl == 1 ? 0.0 : (j == fl - 1 ? 1.0 : double(j) * step_in);
     if (j >= N - fl) {
@@ -81,8 +86,8 @@ struct SimStorer {
     const cd z = cmul(y, w[j]);
     const double f = fade(int(j));
     const int r = row0 + 2 * g;
-    if (r < rows) out[size_t(r) * stride + j] = z.x * f;
-    if (r + 1 < rows) out[size_t(r + 1) * stride + j] = z.y * f;
+    if (r < rows) out[size_t(r) * stride + j] = unexp ? ldexp(z.x * f, unexp[r / rows_per_base]) : z.x * f;
+    if (r + 1 < rows) out[size_t(r + 1) * stride + j] = unexp ? ldexp(z.y * f, unexp[(r + 1) / rows_per_base]) : z.y * f;
   }
 };
 
@@ -123,6 +128,10 @@ __global__ __launch_bounds__(256) void k_norm_compress(const double* in, size_t 
 // Per-mic power-of-two rescale of the path gains: gains reach 1e-63 and two mics share one complex
 // transform, so a mic 1e16 times weaker than its partner would drown in the partner's rounding error.  Scaling a row by
 // 2^-e is exact and cancels bit for bit in normalize_signal (x / max|x|).  One lane per row (K is a handful of paths).
+// The amplitude of the row's BASE signal counts as well: with several bases a row of one base rides with a row of the next
+// (M odd), and fractional_delay packs rows of any amplitude.  That exponent (k_row_exponent) is taken off the base's spectrum
+// in SimLoader, not off the gains, which therefore stay in [1, 2) whatever the base's amplitude; SimStorer multiplies it
+// back where the output is not normalised.
 __global__ __launch_bounds__(256) void k_gain_rescale(const double* in, double* out, int rows, int K) {   // (in place when in == out)
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= rows) return;
@@ -131,6 +140,21 @@ __global__ __launch_bounds__(256) void k_gain_rescale(const double* in, double* 
   const bool scale = top > 0 && isfinite(top);
   const int ex = scale ? ilogb(top) : 0;
   for (int p = 0; p < K; ++p) out[size_t(r) * K + p] = scale ? ldexp(in[size_t(r) * K + p], -ex) : in[size_t(r) * K + p];
+}
+
+// exponent e = ilogb(max |x|) of every row (reduce.h row_exponent: 0 for zero, non-finite and subnormal maxima), one workgroup per row
+__global__ __launch_bounds__(256) void k_row_exponent(const double* __restrict__ x, size_t stride, int N, int* __restrict__ ex) {
+  __shared__ double rd[4];
+  const double* r = x + size_t(blockIdx.x) * stride;
+  double top = 0;
+  bool bad = false;
+  for (int i = threadIdx.x; i < N; i += kLanes) {
+    top = fmax(top, fabs(r[i]));
+    bad = bad || !(r[i] - r[i] == 0.0);
+  }
+  const int nonfinite = __syncthreads_or(bad ? 1 : 0);
+  top = block_max(top, rd, threadIdx.x);
+  if (threadIdx.x == 0) ex[blockIdx.x] = nonfinite ? 0 : row_exponent(top);
 }
 
 // np.sum(sig ** 2) per row (utils.py:413): only the ORDER of the rows' energies matters (argmax picks the reference
@@ -325,10 +349,11 @@ struct RowPairLoader {
   static constexpr const char* kName = "RowPairLoader";    // two real rows per complex transform
   const double* x;
   int N, rows;
+  const int* ex;                                           // exponents of these rows (k_row_exponent): both halves go in at [1, 2)
   __device__ cd operator()(int g, unsigned j) const {
     if (j >= unsigned(N)) return mk(0, 0);
-    const double a = x[size_t(2 * g) * N + j];
-    const double b = 2 * g + 1 < rows ? x[size_t(2 * g + 1) * N + j] : 0.0;
+    const double a = ldexp(x[size_t(2 * g) * N + j], -ex[2 * g]);
+    const double b = 2 * g + 1 < rows ? ldexp(x[size_t(2 * g + 1) * N + j], -ex[2 * g + 1]) : 0.0;
     return mk(a, b);
   }
 };
@@ -337,11 +362,12 @@ struct PlainStorer {
   static constexpr const char* kName = "PlainStorer";
   double* corr;
   size_t stride;
-  int len;
+  int len, rows;
+  const int* ex;                                           // as RowPairLoader::ex: multiplied back
   __device__ void operator()(int g, unsigned j, cd y) const {
     if (j >= unsigned(len)) return;
-    corr[size_t(2 * g) * stride + j] = y.x;
-    corr[size_t(2 * g + 1) * stride + j] = y.y;
+    corr[size_t(2 * g) * stride + j] = ldexp(y.x, ex[2 * g]);
+    corr[size_t(2 * g + 1) * stride + j] = 2 * g + 1 < rows ? ldexp(y.y, ex[2 * g + 1]) : y.y;
   }
 };
 
@@ -368,8 +394,9 @@ __global__ __launch_bounds__(256) void k_xcorr_peak(const double* corr, size_t s
 }  // namespace
 
 // ------------------------------------------------------------------ host-side pipelines
+// `d_gains_in` -> `d_gains` (may be the same table): the path gains rescaled per row by a power of two (k_gain_rescale)
 static int simulate_dev(Engine* e, const double* d_base, int bases, int nbase, double fs, int N, const double* d_delays,
-                        const double* d_gains, int rows, int rows_per_base, int K, int out_len, bool compress,
+                        const double* d_gains_in, double* d_gains, int rows, int rows_per_base, int K, int out_len, bool compress,
                         bool normalize, double* d_out) {
   if (N < 100) return e->fail(PAL_ERR_INVALID, "fractional_delay needs at least 100 samples (fade slice of signal_processing.py:75-78)");
   if (nbase > N) return e->fail(PAL_ERR_INVALID, "base signal longer than total_samples");
@@ -377,8 +404,16 @@ static int simulate_dev(Engine* e, const double* d_base, int bases, int nbase, d
   Plan* pl = nullptr;
   PAL_TRY(e->get_plan(2 * N, nbase, N, &pl));
   void* sp = nullptr;
-  PAL_TRY(e->scratch(kWsSpectra, size_t(bases) * pl->H * sizeof(cd), &sp));
+  PAL_TRY(e->scratch(kWsSpectra, size_t(bases) * pl->H * sizeof(cd) + size_t(bases) * sizeof(int), &sp));
   cd* X = static_cast<cd*>(sp);
+  int* base_exp = reinterpret_cast<int*>(X + size_t(bases) * pl->H);
+  k_row_exponent<<<dim3(bases), dim3(kLanes), 0, e->stream>>>(d_base, size_t(nbase), nbase, base_exp);
+  PAL_TRY(e->check(hipGetLastError(), "k_row_exponent"));
+  k_gain_rescale<<<dim3((rows + 255) / 256), dim3(256), 0, e->stream>>>(d_gains_in, d_gains, rows, K);
+  PAL_TRY(e->check(hipGetLastError(), "k_gain_rescale"));
+  // One base per forward transform: this plan has n = 2 N (even) and keeps N outputs, so it has no prime-factor cut and the
+  // packed forward transform of pfa_forward.h (two frames per transform, which would need the rows' flag words) cannot apply.
+  if (e->pfa_forward_applies(*pl, nbase)) return e->fail(PAL_ERR_INTERNAL, "packed forward transform on a simulation plan");
   PAL_TRY(e->forward_spectra(*pl, d_base, size_t(nbase), bases, nbase, X));
   const Conv& c = pl->inv;
   void* wsp = nullptr;
@@ -391,9 +426,10 @@ static int simulate_dev(Engine* e, const double* d_base, int bases, int nbase, d
   for (int t0 = 0; t0 < ntr; t0 += e->chunk) {
     const int G = ntr - t0 < e->chunk ? ntr - t0 : e->chunk;
     const int r0 = 2 * t0;
-    SimLoader ld{X, d_delays, d_gains, K, rows, rows_per_base, N, r0, val, pl->w};
+    SimLoader ld{X, d_delays, d_gains, K, rows, rows_per_base, N, r0, val, pl->w, base_exp};
     SimStorer st{d_out, size_t(out_len), rows, N, out_len, fl, r0,
-                 fl > 1 ? 1.0 / double(fl - 1) : 0.0, fl > 1 ? -1.0 / double(fl - 1) : 0.0, pl->w};
+                 fl > 1 ? 1.0 / double(fl - 1) : 0.0, fl > 1 ? -1.0 / double(fl - 1) : 0.0, pl->w,
+                 compress || normalize ? nullptr : base_exp, rows_per_base};
     PAL_TRY(launch_cols_fwd(e, c, G, ld, W));
     PAL_TRY(launch_rows(e, c, G, W, true, 1.0));
     PAL_TRY(launch_cols_inv(e, c, G, W, st));
@@ -443,7 +479,8 @@ static int filtfilt_dev(Engine* e, const double* b, int nb, const double* a, int
 }
 
 // full cross-correlation of rows[R][N] against row ref_idx (all in HBM): kpk / win5 / pkabs land in device arrays of R entries
-static int xcorr_dev(Engine* e, const double* x, int R, int N, int ref_idx, int32_t* dk, double* dw, double* dp) {
+// `dex`: device scratch of R ints for the rows' exponents
+static int xcorr_dev(Engine* e, const double* x, int R, int N, int ref_idx, int32_t* dk, double* dw, double* dp, int* dex) {
   if (N > (1 << 20)) return e->fail(PAL_ERR_UNSUPPORTED, "signal longer than 2^20 samples");
   const int len = 2 * N - 1;
   // geometry, tables and kernel-spectrum storage of the convolution are kept per length (sync runs once per frame in
@@ -458,12 +495,14 @@ static int xcorr_dev(Engine* e, const double* x, int R, int N, int ref_idx, int3
   PAL_TRY(e->scratch(kWsWork, size_t(e->chunk) * c.M() * sizeof(cd), &wsp));
   const size_t stride = size_t(len) + 1;
   PAL_TRY(e->scratch(kWsCorr, size_t(2 * e->chunk) * stride * sizeof(double), &dcor));
+  k_row_exponent<<<dim3(R), dim3(kLanes), 0, e->stream>>>(x, size_t(N), N, dex);
+  PAL_TRY(e->check(hipGetLastError(), "k_row_exponent"));
   const int ntr = (R + 1) / 2;
   for (int t0 = 0; t0 < ntr; t0 += e->chunk) {
     const int G = ntr - t0 < e->chunk ? ntr - t0 : e->chunk;
     const int r0 = 2 * t0, nrows = R - r0 < 2 * G ? R - r0 : 2 * G;
-    RowPairLoader ld{x + size_t(r0) * N, N, R - r0};
-    PlainStorer st{static_cast<double*>(dcor), stride, len};
+    RowPairLoader ld{x + size_t(r0) * N, N, R - r0, dex + r0};
+    PlainStorer st{static_cast<double*>(dcor), stride, len, R - r0, dex + r0};
     PAL_TRY(launch_cols_fwd(e, c, G, ld, static_cast<cd*>(wsp)));
     PAL_TRY(launch_rows(e, c, G, static_cast<cd*>(wsp), true, 1.0));
     PAL_TRY(launch_cols_inv(e, c, G, static_cast<cd*>(wsp), st));
@@ -507,13 +546,11 @@ int pal_simulate_multipath(pal_handle h, const double* base, int B, int nbase, d
     if ((rc = e->scratch(kWsStageOut, size_t(rows) * out_len * sizeof(double), &dout)) != PAL_OK) break;
     if ((rc = e->check(hipMemcpyAsync(db, base, size_t(B) * nbase * sizeof(double), hipMemcpyHostToDevice, e->stream), "upload")) != PAL_OK) break;
     if ((rc = e->check(hipMemcpyAsync(dd, delays, size_t(rows) * K * sizeof(double), hipMemcpyHostToDevice, e->stream), "upload")) != PAL_OK) break;
-    // per-mic power-of-two rescale of the gains: k_gain_rescale, in place
+    // (simulate_dev rescales the uploaded gains per microphone by a power of two, in place: SURVEY Q8)
     if ((rc = e->check(hipMemcpyAsync(dg, gains, size_t(rows) * K * sizeof(double), hipMemcpyHostToDevice, e->stream), "upload")) != PAL_OK) break;
-    k_gain_rescale<<<dim3((rows + 255) / 256), dim3(256), 0, e->stream>>>(static_cast<double*>(dg), static_cast<double*>(dg), rows, K);
-    if ((rc = e->check(hipGetLastError(), "k_gain_rescale")) != PAL_OK) break;
     if ((rc = e->check(hipStreamSynchronize(e->stream), "upload sync")) != PAL_OK) break;
-    rc = simulate_dev(e, static_cast<double*>(db), B, nbase, fs, N, static_cast<double*>(dd), static_cast<double*>(dg), rows, M,
-                      K, out_len, true, true, static_cast<double*>(dout));
+    rc = simulate_dev(e, static_cast<double*>(db), B, nbase, fs, N, static_cast<double*>(dd), static_cast<double*>(dg),
+                      static_cast<double*>(dg), rows, M, K, out_len, true, true, static_cast<double*>(dout));
     if (rc != PAL_OK) break;
     rc = e->check(hipMemcpyAsync(out, dout, size_t(rows) * out_len * sizeof(double), hipMemcpyDeviceToHost, e->stream), "download");
   } while (0);
@@ -534,7 +571,7 @@ int pal_fractional_delay(pal_handle h, const double* rows_in, int R, int N, cons
   UP(dd, delays, size_t(R) * sizeof(double));
   UP(dg, ones.data(), size_t(R) * sizeof(double));
   PAL_TRY(e->check(hipStreamSynchronize(e->stream), "upload sync"));
-  PAL_TRY(simulate_dev(e, static_cast<double*>(db), R, N, fs, N, static_cast<double*>(dd), dg, R, 1, 1, N, false, false,
+  PAL_TRY(simulate_dev(e, static_cast<double*>(db), R, N, fs, N, static_cast<double*>(dd), dg, dg, R, 1, 1, N, false, false,
                        static_cast<double*>(dout)));
   DOWN(out, dout, size_t(R) * N * sizeof(double));
   return pal_synchronize(h);
@@ -606,13 +643,13 @@ int pal_xcorr_vs_ref(pal_handle h, const double* rows_in, int R, int N, int ref_
   void *dx = nullptr, *dres = nullptr;
   PAL_TRY(e->scratch(kWsStageIn, size_t(R) * N * sizeof(double), &dx));
   UP(dx, rows_in, size_t(R) * N * sizeof(double));
-  // result block: kpk[R] (int32, padded to 16 bytes) | win5[R][5] | pkabs[R]
+  // result block: kpk[R] (int32, padded to 16 bytes) | win5[R][5] | pkabs[R] | row exponents[R] (int, scratch of xcorr_dev)
   const size_t off_d = (size_t(R) * sizeof(int32_t) + 15) & ~size_t(15);
-  PAL_TRY(e->scratch(kWsStageTable, off_d + size_t(R) * 6 * sizeof(double), &dres));
+  PAL_TRY(e->scratch(kWsStageTable, off_d + size_t(R) * 6 * sizeof(double) + size_t(R) * sizeof(int), &dres));
   int32_t* dk = static_cast<int32_t*>(dres);
   double* dw = reinterpret_cast<double*>(static_cast<char*>(dres) + off_d);
   double* dp = dw + size_t(R) * 5;
-  int rc = xcorr_dev(e, static_cast<const double*>(dx), R, N, ref_idx, dk, dw, dp);
+  int rc = xcorr_dev(e, static_cast<const double*>(dx), R, N, ref_idx, dk, dw, dp, reinterpret_cast<int*>(dp + R));
   if (rc == PAL_OK) rc = e->check(hipMemcpyAsync(kpk, dk, size_t(R) * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "download");
   if (rc == PAL_OK) rc = e->check(hipMemcpyAsync(win5, dw, size_t(R) * 5 * sizeof(double), hipMemcpyDeviceToHost, e->stream), "download");
   if (rc == PAL_OK) rc = e->check(hipMemcpyAsync(pkabs, dp, size_t(R) * sizeof(double), hipMemcpyDeviceToHost, e->stream), "download");
@@ -635,9 +672,7 @@ int pal_simulate_multipath_dev(pal_handle h, const double* d_base, int B, int nb
   const int rows = B * M;
   void* dg = nullptr;
   PAL_TRY(e->scratch(kWsStageTable, size_t(rows) * K * sizeof(double), &dg));
-  k_gain_rescale<<<dim3((rows + 255) / 256), dim3(256), 0, e->stream>>>(d_gains, static_cast<double*>(dg), rows, K);
-  PAL_TRY(e->check(hipGetLastError(), "k_gain_rescale"));
-  return simulate_dev(e, d_base, B, nbase, fs, N, d_delays, static_cast<double*>(dg), rows, M, K, out_len, true, true, d_out);
+  return simulate_dev(e, d_base, B, nbase, fs, N, d_delays, d_gains, static_cast<double*>(dg), rows, M, K, out_len, true, true, d_out);
 }
 
 int pal_filtfilt_dev(pal_handle h, const double* b, int nb, const double* a, int na, const double* zi, const double* d_rows,
@@ -705,16 +740,17 @@ int pal_sync_measure_dev(pal_handle h, const double* d_rows, int B, int M, int N
       if (en[size_t(b) * M + m] != en[size_t(b) * M + m]) { best = m; break; }
     ref_idx[b] = best;
   }
-  // result block for all frames: kpk[R] | win5[R][5] | pkabs[R]
+  // result block for all frames: kpk[R] | win5[R][5] | pkabs[R] | row exponents[R] (int, scratch of xcorr_dev)
   void* dres = nullptr;
   const size_t off_d = (size_t(R) * sizeof(int32_t) + 15) & ~size_t(15);
-  PAL_TRY(e->scratch(kWsStageTable, off_d + size_t(R) * 6 * sizeof(double), &dres));
+  PAL_TRY(e->scratch(kWsStageTable, off_d + size_t(R) * 6 * sizeof(double) + size_t(R) * sizeof(int), &dres));
   int32_t* dk = static_cast<int32_t*>(dres);
   double* dw = reinterpret_cast<double*>(static_cast<char*>(dres) + off_d);
   double* dp = dw + size_t(R) * 5;
   int rc = PAL_OK;
   for (int b = 0; b < B && rc == PAL_OK; ++b)     // (the kernel spectrum is the frame's own reference row: one convolution set-up per frame)
-    rc = xcorr_dev(e, d_rows + size_t(b) * M * N, M, N, ref_idx[b], dk + size_t(b) * M, dw + size_t(b) * M * 5, dp + size_t(b) * M);
+    rc = xcorr_dev(e, d_rows + size_t(b) * M * N, M, N, ref_idx[b], dk + size_t(b) * M, dw + size_t(b) * M * 5, dp + size_t(b) * M,
+                   reinterpret_cast<int*>(dp + R) + size_t(b) * M);
   if (rc == PAL_OK) rc = e->check(hipMemcpyAsync(kpk, dk, size_t(R) * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "download");
   if (rc == PAL_OK) rc = e->check(hipMemcpyAsync(win5, dw, size_t(R) * 5 * sizeof(double), hipMemcpyDeviceToHost, e->stream), "download");
   if (rc == PAL_OK) rc = e->check(hipMemcpyAsync(pkabs, dp, size_t(R) * sizeof(double), hipMemcpyDeviceToHost, e->stream), "download");

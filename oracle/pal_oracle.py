@@ -91,9 +91,10 @@ def select_by_distance(peaks: np.ndarray, heights: np.ndarray, distance: int) ->
     ``distance`` samples (scipy ``_select_by_peak_distance``).  Equal heights: the later
     position wins (stable ascending sort walked from the end) - exact ties are unpinned."""
     m = peaks.shape[0]
-    keep = np.ones(m, dtype=bool)
-    order = np.argsort(heights, kind="stable")
-    for idx in order[::-1]:
+    keep = [True] * m
+    order = np.argsort(heights, kind="stable").tolist()
+    peaks = np.asarray(peaks).tolist()                 # (plain ints: the loop below is the oracle's cost on long rows)
+    for idx in reversed(order):
         if not keep[idx]:
             continue
         k = idx - 1
@@ -104,7 +105,7 @@ def select_by_distance(peaks: np.ndarray, heights: np.ndarray, distance: int) ->
         while k < m and peaks[k] - peaks[idx] < distance:
             keep[k] = False
             k += 1
-    return keep
+    return np.array(keep, dtype=bool)
 
 
 def find_peaks_height_distance(x: np.ndarray, height: float, distance: int) -> Tuple[np.ndarray, np.ndarray]:

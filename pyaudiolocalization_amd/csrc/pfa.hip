@@ -482,7 +482,7 @@ int Engine::pfa_pair_group_fin(const Plan& pl, const cd* permuted, const int4* q
     ProfScope ps(this, corr ? "k_pfa_cols_lean" : "k_pfa_cols_fin", on);
     const dim3 grid(nwg);
     const bool full = (f.n1 - 1) / 2 == f.nch * kPfaTC;
-    // histograms only where the bound sqrt(2 mean(x^2)) on the median cannot decide: multipliers above 2 (or negative)
+    // histograms only where fin_decide's bound on the median (from sum x^2, the maximum set apart) cannot decide: multipliers above 2 (or negative)
     const bool hist = !(a.method > 0 || fa.cheb);
     const int nw = f.nch == 2 ? 2 : (f.nch == 3 && !hist ? 3 : 4);   // (three chunks: three wavefronts where the statistics are per wavefront)
     FinSrc src{Y, f.T, static_cast<const Rader89Tab*>(f.r89)};

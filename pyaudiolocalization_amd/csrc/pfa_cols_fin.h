@@ -73,7 +73,7 @@ struct FinArgs {
   double* corr;                   // null, or [rows][stride]: the pass ALSO stores the correlation rows (the caller wants them, or the plan
   size_t stride;                  //   has no finishing form): nobody polls siblings then, the finisher reads the SNR window from the stored row
   int store_rows;                 // 1: this pass writes the rows (column forms); 0 with corr set: they are there already (k_rows_lean reads them)
-  int cheb;                       // 1: no histograms - the median of |corr| is bounded by sqrt(2 mean(corr^2)) (see fin_decide)
+  int cheb;                       // 1: no histograms - the median of |corr| is bounded through sum(corr^2) (see fin_decide)
 };
 
 struct FinWave {                  // one wavefront's share of the finishing block's merge
@@ -188,7 +188,19 @@ __device__ __forceinline__ void fin_decide(const PeakArgs& pa, const FinArgs& fa
     // A peak at or above mult x that bound passes the threshold of utils.py:145 for certain - and the highest peak of a PHAT
     // row stands 3 to 4 sigma above a median of 0.67 sigma, the bound is 1.41 sigma.  A candidate below the bound is not
     // decided here: the row is flagged and the stored-row path computes its exact median.
-    thi = pa.mult * sqrt(2.0 * s.s2 / double(n)) * (1.0 + 1e-12);
+    // With one sample set apart the bound is tighter: of the others fewer than n / 2 - 1 can have x^2 > t^2 once
+    // t^2 >= (s2 - x_max^2) / (n / 2 - 1), so fewer than n / 2 of all samples lie above t and median(|corr|) <= t.  The maximum of
+    // a PHAT row with one arrival holds a quarter of s2: 0.87 of the plain bound.  It matters where the window's best peak is a
+    // noise peak: the arrival lies outside the lag window, whose lags of little overlap carry the row's lowest noise
+    // (tests/test_gpu_peak_positions.py bounds the rows handed on there).  The difference keeps at least an eighth of s2, so its
+    // rounding error stays below the 1e-12 of slack.
+    double bound2 = 2.0 * s.s2 / double(n);
+    const double rest = s.s2 - vmax * vmax;
+    if (n > 4 && rest >= 0.125 * s.s2) {
+      const double b = rest / (0.5 * double(n) - 1.0);
+      if (b < bound2) bound2 = b;
+    }
+    thi = pa.mult * sqrt(bound2) * (1.0 + 1e-12);
     tlo = -INFINITY;
   }
 

@@ -22,7 +22,7 @@ for case in range(cases):
     med = None if rng.random() < 0.4 else float(rng.choice([0.0005, 0.002, 0.01, 0.05]))
     method = "median" if rng.random() < 0.7 else "adaptive"
     mult = float(rng.choice([1.0, 0.5, 2.0, 6.0]))
-    kind = rng.integers(0, 4)
+    kind = rng.integers(0, 5)
     base = rng.standard_normal(L + 64)
     if kind == 0:                                   # independent noise
         frames = rng.standard_normal((mics, L))
@@ -31,8 +31,11 @@ for case in range(cases):
     elif kind == 2:                                 # tones (ill-conditioned PHAT)
         t = np.arange(L) / fs
         frames = np.stack([np.sin(2 * np.pi * 440 * (t + d / fs)) for d in rng.integers(0, 20, mics)]) + 1e-3 * rng.standard_normal((mics, L))
-    else:                                           # sparse / partly silent
+    elif kind == 3:                                 # sparse / partly silent
         frames = rng.standard_normal((mics, L)) * (rng.random((mics, L)) < 0.05)
+    else:                                           # impulses at random positions: the row's peak anywhere in 0 .. n - 1, not only at 0 .. 63
+        frames = rng.standard_normal((mics, L))     # (amplitude sqrt(L): tests/peak_positions.py says why not more)
+        frames[np.arange(mics), rng.integers(0, L, mics)] += np.sqrt(L)
     if rng.random() < 0.15:                         # a silent microphone: exactly zero rows in the reference
         frames[int(rng.integers(0, mics))] = 0.0
     if int(fs * 0.001) < 1:
@@ -52,7 +55,7 @@ for case in range(cases):
         c = O.phat_correlation(frames[i[p]], frames[j[p]])
         gap = max(abs(c[got["k_sel"][p]] - c[want["k_sel"][p]]), abs(c[got["k_argmax"][p]] - c[want["k_argmax"][p]]))
         noise_floor = np.median(np.abs(c)) <= 1e-12 * np.max(np.abs(c))    # the threshold itself is FFT rounding noise
-        if kind >= 2 and (gap <= 1e-12 * max(1.0, np.max(np.abs(c))) or noise_floor):
+        if kind in (2, 3) and (gap <= 1e-12 * max(1.0, np.max(np.abs(c))) or noise_floor):
             ties += 1
         else:
             bad += 1

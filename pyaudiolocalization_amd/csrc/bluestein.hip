@@ -273,89 +273,27 @@ __global__ __launch_bounds__(256) void k_flag_scatter(const pal_pair_record* __r
 }
 
 // ------------------------------------------------------------------ plans
-const cd* Engine::stage_table(int ln) {
-  if (!stage_tw[ln]) {
+const cd* Engine::stage_table(int ln, bool compact) {
+  cd*& slot = compact ? stage_twc[ln] : stage_tw[ln];
+  if (!slot) {
     cd* p = nullptr;
     if (hipMalloc(&p, sizeof(cd) << ln) != hipSuccess) return nullptr;
     (void)hipMemsetAsync(p, 0, sizeof(cd) << ln, stream);
-    k_make_stage_tw<<<dim3(((1 << ln) + 255) / 256), dim3(256), 0, stream>>>(p, ln, false);
-    stage_tw[ln] = p;
+    k_make_stage_tw<<<dim3(((1 << ln) + 255) / 256), dim3(256), 0, stream>>>(p, ln, compact);
+    slot = p;
   }
-  return stage_tw[ln];
+  return slot;
 }
 
-const cd* Engine::stage_table_compact(int ln) {
-  if (!stage_twc[ln]) {
-    cd* p = nullptr;
-    if (hipMalloc(&p, sizeof(cd) << ln) != hipSuccess) return nullptr;
-    (void)hipMemsetAsync(p, 0, sizeof(cd) << ln, stream);
-    k_make_stage_tw<<<dim3(((1 << ln) + 255) / 256), dim3(256), 0, stream>>>(p, ln, true);
-    stage_twc[ln] = p;
-  }
-  return stage_twc[ln];
-}
-
-// Convolution geometry for at least `needed` points: the smaller of 2^k and 3 * 2^k (k >= 12 for the latter, so
-// that a transform is a whole number of 4096-point row tiles).
+// geometry (plan_geometry.h) -> twiddle tables -> storage of the chirp spectrum and the four-step twiddles
 int Engine::alloc_conv(Conv& c, size_t needed) {
-  int lm = ceil_log2(needed);
-  if (lm < 12) lm = 12;
-  if (lm > 22) return fail(PAL_ERR_UNSUPPORTED, "convolution of %zu points exceeds 2^22", needed);
-  c.r3 = false;
-  c.m = size_t(1) << lm;
-  c.l2 = lm <= 19 ? (lm - 6 < 10 ? lm - 6 : 10) : 11;
-  c.l1 = lm - c.l2;
-  const int k3 = lm - 2;                                   // 3 * 2^(lm-2) = 0.75 * 2^lm
-  if (allow_r3 && k3 >= 12 && (size_t(3) << k3) >= needed) {
-    int l2 = k3 - 4 < 10 ? k3 - 4 : 10;
-    int l1 = k3 - l2;
-    if (l1 > 8) { l2 = 11; l1 = k3 - l2; }
-    if (l1 >= 4 && l1 <= 8) {
-      c.r3 = true;
-      c.m = size_t(3) << k3;
-      c.l1 = l1;
-      c.l2 = l2;
-    }
-  }
-  // Register-resident rows (conv_kernels.h k_colsreg_* / k_rowsreg) where the columns then fit one lane comfortably: rows
-  // of 4096 points with 12 ... 24-point columns, or rows of 8192 points with 6 ... 24-point columns (measured on C2 / C3 / C5
-  // and at n = 88 203 with the prime-factor route off: +13 ... +19 % over the LDS-tile passes either way, the shorter rows
-  // ahead where both fit; 32- and 48-point columns need 250 registers in one lane, so they are shared by two neighbouring
-  // lanes (k_colsreg2_*, rows of 8192 points: C4's 393 216 = 48 x 8192, +5 %).  A column length only needs a DFT that fits one lane - 2^a, 3 * 2^a, or 2 x 9 / 10 / 11
-  // (reg_fft.h reg_dft) - so the convolution length is the smallest M1 x 2^12 / 2^13 that holds the sequence, in steps
-  // of about 10 % instead of the 2^k / 3 * 2^k ladder (88 203 points: 22 x 8192 = 180 224 instead of 196 608).
-  // PAL_FOUR_REG = 12 / 13 forces a row length (columns up to 48 points then), 0 turns the route off.
-  c.reg = false;
-  if (four_reg != 0) {
-    static const int kCols[] = {6, 8, 12, 16, 18, 20, 22, 24, 32, 48};
-    size_t best_m = 0;
-    int best_lr = 0, best_m1 = 0;
-    for (int lr = 12; lr <= 13; ++lr) {
-      if ((four_reg == 12 || four_reg == 13) && lr != four_reg) continue;
-      for (int m1 : kCols) {
-        if (lr == 12 && m1 < 12) continue;
-        if (m1 > 24 && lr != 13) continue;                 // 32- / 48-point columns: two lanes per column, rows of 8192
-        const size_t m = size_t(m1) << lr;
-        if (m < needed || m > c.m) continue;               // (never longer than the 2^k / 3 * 2^k choice)
-        if (!best_m || m < best_m) { best_m = m; best_lr = lr; best_m1 = m1; }   // ties: the shorter rows (lr = 12 comes first)
-      }
-    }
-    if (best_m) {
-      c.reg = true;
-      c.m = best_m;
-      c.m1r = best_m1;
-      c.l2 = best_lr;
-      c.l1 = 0;
-      c.r3 = false;
-      if (!stage_table(best_lr)) return fail(PAL_ERR_NOMEM, "twiddle tables");
-    }
-  }
-  if (!c.reg && (!stage_table(c.l1) || !stage_table(c.l2))) return fail(PAL_ERR_NOMEM, "twiddle tables");
-  PAL_HIP(hipMalloc(&c.chat, c.m * sizeof(cd)));
+  if (!conv_geometry(needed, plan_sw, &c.g)) return fail(PAL_ERR_UNSUPPORTED, "convolution of %zu points exceeds 2^22", needed);
+  if ((!c.g.reg() && !stage_table(c.g.l1)) || !stage_table(c.g.l2)) return fail(PAL_ERR_NOMEM, "twiddle tables");
+  PAL_HIP(hipMalloc(&c.chat, c.M() * sizeof(cd)));
   PAL_HIP(hipMalloc(&c.twA, sizeof(cd) * c.M1()));
-  PAL_HIP(hipMalloc(&c.twB, sizeof(cd) << c.l2));
+  PAL_HIP(hipMalloc(&c.twB, sizeof(cd) * c.M2()));
   k_make_roots<<<dim3((c.M1() + 255) / 256), dim3(256), 0, stream>>>(c.twA, c.M1(), double(c.M1()));
-  k_make_roots<<<dim3(((1 << c.l2) + 255) / 256), dim3(256), 0, stream>>>(c.twB, 1 << c.l2, double(c.m));
+  k_make_roots<<<dim3((c.M2() + 255) / 256), dim3(256), 0, stream>>>(c.twB, c.M2(), double(c.M()));
   return check(hipGetLastError(), "k_make_roots");
 }
 
@@ -555,7 +493,7 @@ int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4
   }
   // who transforms a launch group and who computes its rows' statistics: one decision per call (pair_route.h)
   const Pfa& f = pl.pfa;
-  const PairRoute route = pair_route(RouteIn{n, pl.nout, pfa, f.n1, f.n2, f.nch, f.lm, f.r89 != nullptr, table != nullptr, corr_out != nullptr,
+  const PairRoute route = pair_route(RouteIn{n, pl.nout, pfa, f.n1, f.n2, f.nch, f.lm, f.r89, table != nullptr, corr_out != nullptr,
                                              ksel_multi != nullptr, npairs, stored_only, prm.num_peaks, prm.threshold_method, prm.threshold_multiplier,
                                              fin_cols, fuse_peaks, lean_store, rows_lean, rows_lean_min});
   // the finishing passes and k_rows_lean write one flag per pair: 1 = resolved at the end of this call from stored rows

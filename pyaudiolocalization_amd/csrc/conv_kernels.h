@@ -454,24 +454,37 @@ void k_rowsreg(cd* __restrict__ W, const cd* __restrict__ chat, int rows, int G,
   }
 }
 
-#define PAL_SWITCH_M1(m1, l2, ...)                                 \
-  switch ((l2) * 100 + (m1)) {                                     \
-    case 1306: { constexpr int MM = 6, LR = 13; __VA_ARGS__; } break;   \
-    case 1308: { constexpr int MM = 8, LR = 13; __VA_ARGS__; } break;   \
-    case 1312: { constexpr int MM = 12, LR = 13; __VA_ARGS__; } break;  \
-    case 1316: { constexpr int MM = 16, LR = 13; __VA_ARGS__; } break;  \
-    case 1318: { constexpr int MM = 18, LR = 13; __VA_ARGS__; } break;  \
-    case 1320: { constexpr int MM = 20, LR = 13; __VA_ARGS__; } break;  \
-    case 1322: { constexpr int MM = 22, LR = 13; __VA_ARGS__; } break;  \
-    case 1324: { constexpr int MM = 24, LR = 13; __VA_ARGS__; } break;  \
+// the register geometries, as plan_geometry.h kRegGeoms lists them: rows of 2^LR points, MM-point columns (32 and 48: two lanes per column)
+#define PAL_SWITCH_REG(g, ...)                                     \
+  switch ((g).l2 * 100 + (g).m1) {                                 \
     case 1212: { constexpr int MM = 12, LR = 12; __VA_ARGS__; } break;  \
     case 1216: { constexpr int MM = 16, LR = 12; __VA_ARGS__; } break;  \
     case 1218: { constexpr int MM = 18, LR = 12; __VA_ARGS__; } break;  \
     case 1220: { constexpr int MM = 20, LR = 12; __VA_ARGS__; } break;  \
     case 1222: { constexpr int MM = 22, LR = 12; __VA_ARGS__; } break;  \
     case 1224: { constexpr int MM = 24, LR = 12; __VA_ARGS__; } break;  \
-    default: return e->fail(PAL_ERR_INTERNAL, "register column pass of %d points, rows of 2^%d", m1, l2); \
+    case 1312: { constexpr int MM = 12, LR = 13; __VA_ARGS__; } break;  \
+    case 1316: { constexpr int MM = 16, LR = 13; __VA_ARGS__; } break;  \
+    case 1318: { constexpr int MM = 18, LR = 13; __VA_ARGS__; } break;  \
+    case 1320: { constexpr int MM = 20, LR = 13; __VA_ARGS__; } break;  \
+    case 1322: { constexpr int MM = 22, LR = 13; __VA_ARGS__; } break;  \
+    case 1324: { constexpr int MM = 24, LR = 13; __VA_ARGS__; } break;  \
+    case 1332: { constexpr int MM = 32, LR = 13; __VA_ARGS__; } break;  \
+    case 1348: { constexpr int MM = 48, LR = 13; __VA_ARGS__; } break;  \
+    default: return e->fail(PAL_ERR_INTERNAL, "register column pass of %d points, rows of 2^%d", (g).m1, (g).l2); \
   }
+
+// the column kernels of a register geometry: one lane per column up to 24 points, two lanes beyond
+template <int M1, int LR, class Loader> static constexpr auto colsreg_fwd() {
+  if constexpr (M1 > 24) return &k_colsreg2_fwd<M1, LR, Loader>; else return &k_colsreg_fwd<M1, LR, Loader>;
+}
+template <int M1, int LR, class Storer> static constexpr auto colsreg_inv() {
+  if constexpr (M1 > 24) return &k_colsreg2_inv<M1, LR, Storer>; else return &k_colsreg_inv<M1, LR, Storer>;
+}
+// workgroups of such a pass over G transforms: kRegCols columns each, half of that with two lanes per column
+static unsigned colsreg_grid(const ConvGeom& g, int G, int xcd) {
+  return row_work_grid(G, (1 << g.l2) / (g.kind == ConvKind::kReg2 ? kRegCols / 2 : kRegCols), xcd);
+}
 
 // ------------------------------------------------------------------ launch helpers
 #define PAL_SWITCH_L(l, ...)                                       \
@@ -498,56 +511,65 @@ void k_rowsreg(cd* __restrict__ W, const cd* __restrict__ chat, int rows, int G,
 template <class Loader>
 static int launch_cols_fwd(Engine* e, const Conv& c, int G, Loader ld, cd* W, hipStream_t on = nullptr) {
   if (!on) on = e->stream;
+  const ConvGeom& g = c.g;
   char name[64];
-  if (c.reg) snprintf(name, sizeof name, "k_colsreg_fwd<%d,%s>", c.M1(), Loader::kName);
-  else snprintf(name, sizeof name, "k_cols%s_fwd<%d,%s>", c.r3 ? "3" : "", c.l1, Loader::kName);
+  if (g.reg()) snprintf(name, sizeof name, "k_colsreg_fwd<%d,%s>", g.m1, Loader::kName);
+  else snprintf(name, sizeof name, "k_cols%s_fwd<%d,%s>", g.kind == ConvKind::kLds3 ? "3" : "", g.l1, Loader::kName);
   ProfScope ps(e, name, on);
-  if (c.reg) {
-    const int xcd = e->xcd_rows && G > 1;
-    const bool pair = c.M1() > 24;                             // two lanes per column
-    const unsigned grid = row_work_grid(G, (1 << c.l2) / (pair ? kRegCols / 2 : kRegCols), xcd);
-    if (pair) {
-      if (c.M1() == 48) k_colsreg2_fwd<48, 13, Loader><<<dim3(grid), dim3(kRegCols), 0, on>>>(ld, W, G, c.twA, c.twB, xcd);
-      else if (c.M1() == 32) k_colsreg2_fwd<32, 13, Loader><<<dim3(grid), dim3(kRegCols), 0, on>>>(ld, W, G, c.twA, c.twB, xcd);
-      else return e->fail(PAL_ERR_INTERNAL, "two-lane column pass of %d points", c.M1());
-    } else
-    PAL_SWITCH_M1(c.M1(), c.l2, k_colsreg_fwd<MM, LR, Loader><<<dim3(grid), dim3(kRegCols), 0, on>>>(ld, W, G, c.twA, c.twB, xcd));
-  } else if (c.r3) {
-    const int tiles = int(c.M() / kPoints3), xcd = e->xcd_rows && G > 1;
-    PAL_SWITCH_L3(c.l1, k_cols3_fwd<LL, Loader><<<dim3(row_work_grid(G, tiles, xcd)), dim3(kLanes3), 0, on>>>(
-                            ld, W, c.l2, G, e->stage_table(LL), c.twA, c.twB, tiles, xcd));
-  } else {
-    const int tiles = int(c.M() / kPoints), xcd = e->xcd_rows && G > 1;
-    PAL_SWITCH_L(c.l1, k_cols_fwd<LL, Loader><<<dim3(row_work_grid(G, tiles, xcd)), dim3(kLanes), 0, on>>>(
-                           ld, W, c.l2, G, e->stage_table(LL), c.twA, c.twB, tiles, xcd));
+  const int xcd = e->xcd_rows && G > 1;
+  switch (g.kind) {
+    case ConvKind::kReg:
+    case ConvKind::kReg2:
+      PAL_SWITCH_REG(g, colsreg_fwd<MM, LR, Loader>()<<<dim3(colsreg_grid(g, G, xcd)), dim3(kRegCols), 0, on>>>(ld, W, G, c.twA, c.twB, xcd));
+      break;
+    case ConvKind::kLds3: {
+      const int tiles = int(g.m / kPoints3);
+      PAL_SWITCH_L3(g.l1, k_cols3_fwd<LL, Loader><<<dim3(row_work_grid(G, tiles, xcd)), dim3(kLanes3), 0, on>>>(
+                              ld, W, g.l2, G, e->stage_table(LL), c.twA, c.twB, tiles, xcd));
+      break;
+    }
+    case ConvKind::kLds: {
+      const int tiles = int(g.m / kPoints);
+      PAL_SWITCH_L(g.l1, k_cols_fwd<LL, Loader><<<dim3(row_work_grid(G, tiles, xcd)), dim3(kLanes), 0, on>>>(
+                             ld, W, g.l2, G, e->stage_table(LL), c.twA, c.twB, tiles, xcd));
+      break;
+    }
   }
   return e->check(hipGetLastError(), "k_cols_fwd");
 }
 
 static int launch_rows(Engine* e, const Conv& c, int G, cd* W, bool conv, double scale, hipStream_t on = nullptr) {
   if (!on) on = e->stream;
+  const ConvGeom& g = c.g;
   char name[64];
-  snprintf(name, sizeof name, c.reg ? "k_rowsreg<%d,%s>" : "k_rows<%d,%s>", c.l2, conv ? "conv" : "fwd");
+  snprintf(name, sizeof name, g.reg() ? "k_rowsreg<%d,%s>" : "k_rows<%d,%s>", g.l2, conv ? "conv" : "fwd");
   ProfScope ps(e, name, on);
-  const int tiles = int(c.M() / kPoints), xcd = e->xcd_rows && G > 1;
-  const unsigned grid = row_work_grid(G, tiles, xcd);
-  if (c.reg) {
-    const cd* tws = e->stage_table(c.l2);
-    if (!tws) return e->fail(PAL_ERR_NOMEM, "twiddle tables");
-    const unsigned rgrid = row_work_grid(G, c.M1(), xcd);
-    if (c.l2 == 13) {
-      constexpr int lanes = BigTile<13, 32>::kLanes;
-      if (conv) k_rowsreg<13, true><<<dim3(rgrid), dim3(lanes), 0, on>>>(W, c.chat, c.M1(), G, tws, scale, xcd);
-      else k_rowsreg<13, false><<<dim3(rgrid), dim3(lanes), 0, on>>>(W, c.chat, c.M1(), G, tws, scale, xcd);
-    } else {
-      constexpr int lanes = BigTile<12, 32>::kLanes;
-      if (conv) k_rowsreg<12, true><<<dim3(rgrid), dim3(lanes), 0, on>>>(W, c.chat, c.M1(), G, tws, scale, xcd);
-      else k_rowsreg<12, false><<<dim3(rgrid), dim3(lanes), 0, on>>>(W, c.chat, c.M1(), G, tws, scale, xcd);
+  const int xcd = e->xcd_rows && G > 1;
+  switch (g.kind) {
+    case ConvKind::kReg:
+    case ConvKind::kReg2: {                                    // one workgroup per row of 2^12 / 2^13 points
+      const cd* tws = e->stage_table(g.l2);
+      if (!tws) return e->fail(PAL_ERR_NOMEM, "twiddle tables");
+      const unsigned grid = row_work_grid(G, g.m1, xcd);
+      if (g.l2 == 13) {
+        constexpr int lanes = BigTile<13, 32>::kLanes;
+        if (conv) k_rowsreg<13, true><<<dim3(grid), dim3(lanes), 0, on>>>(W, c.chat, g.m1, G, tws, scale, xcd);
+        else k_rowsreg<13, false><<<dim3(grid), dim3(lanes), 0, on>>>(W, c.chat, g.m1, G, tws, scale, xcd);
+      } else {
+        constexpr int lanes = BigTile<12, 32>::kLanes;
+        if (conv) k_rowsreg<12, true><<<dim3(grid), dim3(lanes), 0, on>>>(W, c.chat, g.m1, G, tws, scale, xcd);
+        else k_rowsreg<12, false><<<dim3(grid), dim3(lanes), 0, on>>>(W, c.chat, g.m1, G, tws, scale, xcd);
+      }
+      break;
     }
-  } else if (conv) {
-    PAL_SWITCH_L(c.l2, k_rows<LL, true><<<dim3(grid), dim3(kLanes), 0, on>>>(W, c.chat, c.M(), G, e->stage_table(LL), scale, tiles, xcd));
-  } else {
-    PAL_SWITCH_L(c.l2, k_rows<LL, false><<<dim3(grid), dim3(kLanes), 0, on>>>(W, c.chat, c.M(), G, e->stage_table(LL), scale, tiles, xcd));
+    case ConvKind::kLds3:
+    case ConvKind::kLds: {
+      const int tiles = int(g.m / kPoints);
+      const unsigned grid = row_work_grid(G, tiles, xcd);
+      if (conv) { PAL_SWITCH_L(g.l2, k_rows<LL, true><<<dim3(grid), dim3(kLanes), 0, on>>>(W, c.chat, g.m, G, e->stage_table(LL), scale, tiles, xcd)); }
+      else { PAL_SWITCH_L(g.l2, k_rows<LL, false><<<dim3(grid), dim3(kLanes), 0, on>>>(W, c.chat, g.m, G, e->stage_table(LL), scale, tiles, xcd)); }
+      break;
+    }
   }
   return e->check(hipGetLastError(), "k_rows");
 }
@@ -555,28 +577,26 @@ static int launch_rows(Engine* e, const Conv& c, int G, cd* W, bool conv, double
 template <class Storer>
 static int launch_cols_inv(Engine* e, const Conv& c, int G, const cd* W, Storer st, hipStream_t on = nullptr) {
   if (!on) on = e->stream;
+  const ConvGeom& g = c.g;
   char name[64];
-  if (c.reg) snprintf(name, sizeof name, "k_colsreg_inv<%d,%s>", c.M1(), Storer::kName);
-  else snprintf(name, sizeof name, "k_cols%s_inv<%d,%s>", c.r3 ? "3" : "", c.l1, Storer::kName);
+  if (g.reg()) snprintf(name, sizeof name, "k_colsreg_inv<%d,%s>", g.m1, Storer::kName);
+  else snprintf(name, sizeof name, "k_cols%s_inv<%d,%s>", g.kind == ConvKind::kLds3 ? "3" : "", g.l1, Storer::kName);
   ProfScope ps(e, name, on);
-  if (c.reg) {
-    const int xcd = e->xcd_rows && G > 1;
-    const bool pair = c.M1() > 24;                             // two lanes per column
-    const unsigned grid = row_work_grid(G, (1 << c.l2) / (pair ? kRegCols / 2 : kRegCols), xcd);
-    if (pair) {
-      if (c.M1() == 48) k_colsreg2_inv<48, 13, Storer><<<dim3(grid), dim3(kRegCols), 0, on>>>(W, st, G, c.twA, c.twB, xcd);
-      else if (c.M1() == 32) k_colsreg2_inv<32, 13, Storer><<<dim3(grid), dim3(kRegCols), 0, on>>>(W, st, G, c.twA, c.twB, xcd);
-      else return e->fail(PAL_ERR_INTERNAL, "two-lane column pass of %d points", c.M1());
-    } else
-    PAL_SWITCH_M1(c.M1(), c.l2, k_colsreg_inv<MM, LR, Storer><<<dim3(grid), dim3(kRegCols), 0, on>>>(W, st, G, c.twA, c.twB, xcd));
-  } else if (c.r3) {
-    const unsigned grid = unsigned(size_t(G) * (c.M() / kPoints3));
-    PAL_SWITCH_L3(c.l1, k_cols3_inv<LL, Storer><<<dim3(grid), dim3(kLanes3), 0, on>>>(W, st, c.l2, G, e->stage_table(LL),
-                                                                                              c.twA, c.twB));
-  } else {
-    const unsigned grid = unsigned(size_t(G) * (c.M() / kPoints));
-    PAL_SWITCH_L(c.l1, k_cols_inv<LL, Storer><<<dim3(grid), dim3(kLanes), 0, on>>>(W, st, c.l2, G, e->stage_table(LL),
-                                                                                          c.twA, c.twB));
+  switch (g.kind) {
+    case ConvKind::kReg:
+    case ConvKind::kReg2: {
+      const int xcd = e->xcd_rows && G > 1;
+      PAL_SWITCH_REG(g, colsreg_inv<MM, LR, Storer>()<<<dim3(colsreg_grid(g, G, xcd)), dim3(kRegCols), 0, on>>>(W, st, G, c.twA, c.twB, xcd));
+      break;
+    }
+    case ConvKind::kLds3:
+      PAL_SWITCH_L3(g.l1, k_cols3_inv<LL, Storer><<<dim3(unsigned(size_t(G) * (g.m / kPoints3))), dim3(kLanes3), 0, on>>>(
+                              W, st, g.l2, G, e->stage_table(LL), c.twA, c.twB));
+      break;
+    case ConvKind::kLds:
+      PAL_SWITCH_L(g.l1, k_cols_inv<LL, Storer><<<dim3(unsigned(size_t(G) * (g.m / kPoints))), dim3(kLanes), 0, on>>>(
+                             W, st, g.l2, G, e->stage_table(LL), c.twA, c.twB));
+      break;
   }
   return e->check(hipGetLastError(), "k_cols_inv");
 }

@@ -14,48 +14,38 @@
 #include "fin_scratch.h"
 #include "fft_core.h"
 #include "pair_route.h"
+#include "plan_geometry.h"
 #include "peak_types.h"
 #include "resample_math.h"
 
 namespace pal {
 
-// One circular convolution of length M = M1 x M2 (four-step, both factors in LDS).
-// M2 = 2^l2; M1 = 2^l1, or 3 * 2^l1 (r3) when the 3 * 2^k length is the smaller fit.
+// One circular convolution of length M = M1 x M2 (four-step): its geometry (plan_geometry.h) and device tables.
 struct FinArgs;     // pfa_cols_fin.h
 
 struct Conv {
-  int l1 = 0, l2 = 0;
-  bool r3 = false;
-  bool reg = false;              // rows of 8192 points in registers, columns of m1r points in the registers of one lane (conv_kernels.h)
-  int m1r = 0;
-  size_t m = 0;                  // points per transform
+  ConvGeom g;
   cd* chat = nullptr;            // FFT_M of the chirp kernel in [k1][k2] order, pre-scaled
   cd* twA = nullptr;             // exp(-2 pi i q / M1), q < M1
   cd* twB = nullptr;             // exp(-2 pi i r / M),  r < M2
-  size_t M() const { return m; }
-  int M1() const { return reg ? m1r : (r3 ? 3 : 1) << l1; }
-  int M2() const { return 1 << l2; }
+  size_t M() const { return g.m; }
+  int M1() const { return g.m1; }
+  int M2() const { return 1 << g.l2; }
 };
 
 // Prime-factor cut n = N1 x N2 (coprime, both odd) of the inverse PHAT transform (pfa.hip): N2-point DFTs as
 // chirp convolutions of length M = 2^lm that never leave LDS, then dense N1-point DFTs down the columns.
-struct Pfa {
-  int n1 = 0, n2 = 0;      // N1 <= 127 (dense), N2 <= M/2 (in-LDS Bluestein)
-  int lm = 0;              // log2 M: 10..12 two tiles per workgroup in LDS (pfa_kernels.h), 13..14 one register-resident tile (pfa_big.h)
-  int u1 = 0;              // N2^-1 mod N1
-  long long e1 = 0, e2 = 0;   // CRT idempotents: k = (e1 k1 + e2 k2) mod n
-  int nch = 1;             // accumulator chunks of the column pass
-  cd* b = nullptr;         // chirp exp(i pi u2 j^2 / N2), j < N2 (u2 = N1^-1 mod N2, made even)
+struct Pfa : PfaSplit {     // the cut itself (plan_geometry.h: n1, n2, lm, u1, u2, e1, e2, nch, rader, r89) and its device tables
+  cd* b = nullptr;         // chirp exp(i pi u2 j^2 / N2), j < N2
   cd* hhat = nullptr;      // FFT_M of the conjugate chirp kernel, scaled by 1 / (M n)
   cd* r1 = nullptr;        // exp(-2 pi i q / N1), q < N1
   double* T = nullptr;     // cos / sin (2 pi j t / N1) in the column pass's chunked order
   int2* rowtab = nullptr;  // per row of Y: (u1 row mod N1, its step between outputs of a last-stage butterfly)
-  // Rader variant of the row pass (pfa_rader.h) when N2 is prime and N2 - 1 = 11 x 9 x 10
-  bool rader = false;
+  // `rader`: the Rader variant of the row pass (pfa_rader.h), N2 prime and N2 - 1 = 11 x 9 x 10
   cd *rd_bhat_f = nullptr;   // forward direction (pfa_forward.h): FFT_L of exp(-2 pi i u2 g^s / N2) / L
   cd* rd_bhat = nullptr;     // 3-D spectrum of the Rader kernel sequence in prime-factor positions (mixed_radix.h)
   int *rd_qidx = nullptr, *rd_ridx = nullptr;
-  void* r89 = nullptr;       // N1 = 89: tables of the Rader column transform (pfa_rader89.h: Rader89Tab)
+  void* r89_tab = nullptr;   // `r89`, N1 = 89: tables of the Rader column transform (pfa_rader89.h: Rader89Tab)
   int rows() const { return (n1 + 1) / 2; }   // spectrum rows k1 <= (N1-1)/2 kept by the permuted layout
   bool on() const { return n1 > 0; }
 };
@@ -123,13 +113,9 @@ struct Engine {
   bool lean_store = true;          // PAL_LEAN_STORE=0: stored rows keep the round-2 statistics (pfa_cols_stats.h / three launches) + k_peak_finish
   int debug_memo = 0;              // PAL_DEBUG_MEMO=<n>: shrinks the distance rule's on-chip memo / stack (tests of its slow path)
   bool one_stream = false;         // PAL_OVERLAP=0: every launch on `stream` (default: launch groups rotate over three streams)
-  bool allow_r3 = true;            // PAL_RADIX3=0 forces power-of-two convolution lengths
-  bool allow_pfa = true;           // PAL_PFA=0 keeps the PHAT inverse on the four-step chirp convolution
-  bool allow_rader = true;         // PAL_RADER=0 keeps the row pass on the in-LDS chirp convolution
-  int four_reg = -1;               // PAL_FOUR_REG: register-resident rows of the four-step route: -1 choose, 12 / 13 force 2^12 / 2^13, 0 = LDS tiles only
+  PlanSwitches plan_sw;            // PAL_RADIX3, PAL_FOUR_REG, PAL_PFA, PAL_PFA_BIG, PAL_RADER, PAL_R89: what shapes a plan (plan_geometry.h)
   bool xcd_rows = true;            // PAL_XCD_ROWS=0: row passes in plain workgroup order (pfa_kernels.h: row_work_item)
   bool rows_shared = true;         // PAL_ROWS_SHARED=0: the Rader row pass reads all four spectrum rows even when two are the same (pfa_rader.h)
-  bool allow_big = true;           // PAL_PFA_BIG=0: no register-resident row tiles (N2 <= 2048 only, as in round 1)
   std::string err;
   static constexpr int kDefaultChunk = 128;
   int chunk = kDefaultChunk;                    // transforms per launch group (forward spectra, simulation, synchronisation)
@@ -184,9 +170,8 @@ struct Engine {
     return rc;
   }
   int status_words(int** out) { return scratch(kWsStatus, kStatusWords * sizeof(int), out); }   // peak_types.h StatusWord; zeroed when first taken
-  const cd* stage_table(int ln);
-  const cd* stage_table_compact(int ln);
-  int build_pfa(Plan& pl);                  // pfa.hip: choose the split and make the tables (leaves pl.pfa off if none fits)
+  const cd* stage_table(int ln, bool compact = false);   // stage_tw[ln] / stage_twc[ln], made on first use (null: out of memory)
+  int build_pfa(Plan& pl);                  // pfa.hip: the split of plan_geometry.h and its tables, built in pl.pfa (off if no split fits)
   void free_pfa(Pfa& f);
   int build_rader(Pfa& f, long long n, long long u2);   // pfa.hip: Rader tables when N2 is 991
   int pfa_pair_group(const Plan& pl, const cd* permuted, const int4* quads, int G, cd* Y, double* corr, size_t stride,
@@ -261,7 +246,6 @@ struct Engine {
   FinKey fin_key[3];            // the layout of the slot's latest launch (fin_scratch.h: another one zeroes the block)
   unsigned fin_wrap = kFinEpochWrap;   // PAL_DEBUG_FIN_WRAP=<n>: the epoch bound (tests of the reset at the wrap)
   int fin_giveup = 0;           // PAL_DEBUG_FIN_GIVEUP=1: every bounded wait of the pass gives up at once (tests of the stored-row repair)
-  bool allow_r89 = true;      // PAL_R89=0: dense 89-point column DFTs instead of Rader's 8 x 11 convolution (pfa_rader89.h)
   bool fuse_peaks = true;     // PAL_FUSED=0: separate column pass + pivot / stream launches instead of the fused column pass +
                               // peak statistics (pfa_cols_stats.h) where that applies
 };
@@ -281,12 +265,6 @@ struct ProfScope {
     if (slot >= 0) e->prof_end(slot, a, on);
   }
 };
-
-inline int ceil_log2(size_t v) {
-  int l = 0;
-  while ((size_t(1) << l) < v) ++l;
-  return l;
-}
 
 #define PAL_TRY(expr)                \
   do {                               \

@@ -294,15 +294,15 @@ int pal_create(int device, pal_handle* out) {
   env = getenv("PAL_OVERLAP");
   e->one_stream = env && atoi(env) == 0;
   env = getenv("PAL_RADIX3");
-  if (env) e->allow_r3 = atoi(env) != 0;
+  if (env) e->plan_sw.allow_r3 = atoi(env) != 0;
   env = getenv("PAL_PFA");
-  if (env) e->allow_pfa = atoi(env) != 0;
+  if (env) e->plan_sw.allow_pfa = atoi(env) != 0;
   env = getenv("PAL_RADER");
-  if (env) e->allow_rader = atoi(env) != 0;
+  if (env) e->plan_sw.allow_rader = atoi(env) != 0;
   env = getenv("PAL_PFA_BIG");
-  if (env) e->allow_big = atoi(env) != 0;
+  if (env) e->plan_sw.allow_big = atoi(env) != 0;
   env = getenv("PAL_FOUR_REG");
-  if (env) e->four_reg = atoi(env);
+  if (env) e->plan_sw.four_reg = atoi(env) != 0;
   env = getenv("PAL_XCD_ROWS");
   if (env) e->xcd_rows = atoi(env) != 0;
   env = getenv("PAL_ROWS_SHARED");
@@ -312,7 +312,7 @@ int pal_create(int device, pal_handle* out) {
   env = getenv("PAL_FUSED");
   if (env) e->fuse_peaks = atoi(env) != 0;
   env = getenv("PAL_R89");
-  if (env) e->allow_r89 = atoi(env) != 0;
+  if (env) e->plan_sw.allow_r89 = atoi(env) != 0;
   env = getenv("PAL_FIN_SERIAL");
   if (env) e->fin_serial = atoi(env) != 0;
   env = getenv("PAL_FIN");

@@ -47,18 +47,9 @@ namespace pal {
 constexpr int kBig13 = PAL_BIG13_PTS, kBig14 = PAL_BIG14_PTS;
 
 // ------------------------------------------------------------------ plan
-static long long inv_mod(long long a, long long m) {   // a^-1 mod m (gcd = 1), 0 when m == 1
-  if (m == 1) return 0;
-  long long g = m, x = 0, y = 1, aa = a % m;
-  while (aa) {
-    const long long q = g / aa;
-    long long t = g - q * aa; g = aa; aa = t;
-    t = x - q * y; x = y; y = t;
-  }
-  return g == 1 ? ((x % m) + m) % m : -1;
-}
-
-static long long gcd_ll(long long a, long long b) { while (b) { long long t = a % b; a = b; b = t; } return a; }
+// plan_geometry.h is host-only and restates what it needs of the kernels' constants and types
+static_assert(kColChunk == kPfaTC && kColUnroll == kPfaUnr && kRader89 == kR89, "plan_geometry.h against the column pass's constants");
+static_assert(sizeof(RowStep) == sizeof(int2) && sizeof(Cplx) == sizeof(cd), "plan_geometry.h tables are uploaded as they are");
 
 void Engine::free_pfa(Pfa& f) {
   if (f.b) (void)hipFree(f.b);
@@ -66,7 +57,7 @@ void Engine::free_pfa(Pfa& f) {
   if (f.r1) (void)hipFree(f.r1);
   if (f.T) (void)hipFree(f.T);
   if (f.rowtab) (void)hipFree(f.rowtab);
-  if (f.r89) (void)hipFree(f.r89);
+  if (f.r89_tab) (void)hipFree(f.r89_tab);
   for (void* p : {(void*)f.rd_bhat, (void*)f.rd_bhat_f, (void*)f.rd_qidx,
                   (void*)f.rd_ridx})
     if (p) (void)hipFree(p);
@@ -82,176 +73,60 @@ void Engine::free_pfa(Pfa& f) {
     default: return fail(PAL_ERR_INTERNAL, "prime-factor plan with log2 M = %d", lm); \
   }
 
+// host table -> a device allocation of its own
+template <class T, class D> static int upload_table(Engine* e, const std::vector<T>& host, D** dev) {
+  static_assert(sizeof(T) == sizeof(D), "uploaded as it is");
+  if (hipMalloc(dev, host.size() * sizeof(T)) != hipSuccess) return e->fail(PAL_ERR_NOMEM, "prime-factor tables");
+  return e->check(hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice), "prime-factor tables");
+}
+
+// split (plan_geometry.h) -> allocations and uploads -> setup launches, all into pl.pfa: a failure on the way leaves what exists of
+// the cut where get_plan's cleanup frees it
 int Engine::build_pfa(Plan& pl) {
-  pl.pfa = Pfa();
-  const long long n = pl.n;
-  if (!allow_pfa || pl.nout != pl.n || n < 3 || (n & 1) == 0) return PAL_OK;
-  // Best coprime split by a time model fitted to this part (microseconds per packed transform inside a launch group of
-  // 240): a row tile of 2^lm points costs w[lm] - 0.005 / 0.011 / 0.026 for the LDS-resident tiles of
-  // 1024 / 2048 / 4096 points (two per workgroup), 0.050 / 0.145 for the register-resident tiles of 8192 / 16384 (pfa_big.h:
-  // the 16384-point tile runs one workgroup per CU) - and the column pass 1.15e-5 n for its
-  // traffic plus 4e-8 N1 n for the dense N1-point DFTs.  The four-step route: 1.6e-5 per point of its convolution for the
-  // first two passes, 2.2e-5 n for the last pass and the statistics launches, x 0.86 with register-resident rows.  A split that cannot take the fused column
-  // pass (more than four chunks of output indices: N1 > 89) must beat the four-step route by 15 %.
-  static const double kTile[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0.003, 0.005, 0.0113, 0.026, 0.050, 0.145};
-  double best = -1;
-  int bn1 = 0, bn2 = 0, blm = 0;
-  for (long long d = 1; d <= 127 && d <= n; d += 2) {
-    if (n % d) continue;
-    const long long r = n / d;
-    if (r > (allow_big ? 8192 : 2048) || gcd_ll(d, r) != 1) continue;
-    int lm = 9;
-    while ((1ll << lm) < 2 * r - 1) ++lm;
-    // (16384-point tiles run one workgroup per CU for 45 us each: with few rows per transform the rounds of workgroups and the
-    //  per-group fixed costs weigh more than the model says - 24 051 = 3 x 8017 measured 1.41 M pairs/s against 1.84 M on the
-    //  four-step route, 48 k-point lengths break even: profiles/r02_g_length_sweep_*.csv)
-    if (lm == 14 && n < 40000) continue;
-    const int chunks = d > 1 ? int(((d - 1) / 2 + kPfaTC - 1) / kPfaTC) : 1;
-    double cost = double(d) * kTile[lm] + double(n) * (1.15e-5 + 4e-8 * double(d));
-    if (chunks > 4) cost *= 1.15;
-    if (best < 0 || cost < best) { best = cost; bn1 = int(d); bn2 = int(r); blm = lm; }
-  }
-  const double four_step = (1.6e-5 * double(pl.inv.M()) + 2.2e-5 * double(n)) * (pl.inv.reg ? 0.86 : 1.0);
-  if (best < 0 || best > four_step) return PAL_OK;             // the four-step route is no worse
-  // (short transforms are launch-bound, the model does not apply: there the split must also stay within 1.5 x the
-  //  four-step route's points, round 1's rule)
-  if (n < 16384 && size_t(((bn1 + 1) / 2) * (2ll << blm)) > pl.inv.M() + pl.inv.M() / 2) return PAL_OK;
-  Pfa f;
-  f.n1 = bn1; f.n2 = bn2; f.lm = blm;
-  f.u1 = int(inv_mod(bn2, bn1));
-  long long u2 = inv_mod(bn1, bn2);
-  if (bn2 == 1) u2 = 0;
-  f.e1 = (long long)bn2 * f.u1 % n;
-  f.e2 = (long long)bn1 * u2 % n;
-  if (u2 & 1) u2 += bn2;                       // even multiplier: the chirp is periodic mod N2 and symmetric
-  const int h = (bn1 - 1) / 2;
-  f.nch = h > 0 ? (h + kPfaTC - 1) / kPfaTC : 1;
-  const cd* tws = blm >= 13 ? stage_table(blm) : (blm >= 11 ? stage_table_compact(blm) : stage_table(blm));
-  if (!tws || !stage_table(blm)) return fail(PAL_ERR_NOMEM, "twiddle tables");   // (the full table feeds the register twiddles)
-  PAL_HIP(hipMalloc(&f.b, sizeof(cd) * bn2));
-  PAL_HIP(hipMalloc(&f.hhat, sizeof(cd) << blm));
-  PAL_HIP(hipMalloc(&f.r1, sizeof(cd) * bn1));
-  k_make_chirp<<<dim3((bn2 + 255) / 256), dim3(256), 0, stream>>>(f.b, bn2, int(u2));
-  k_make_roots<<<dim3((bn1 + 255) / 256), dim3(256), 0, stream>>>(f.r1, bn1, double(bn1));
-  const double scale = 1.0 / (double(1 << blm) * double(n));   // inverse FFT_M and numpy.fft.ifft's 1/n
-  if (blm == 13) k_pfa_hhat_big<13, kBig13><<<dim3(1), dim3(BigTile<13, kBig13>::kLanes), 0, stream>>>(f.b, bn2, f.hhat, scale, tws);
-  else if (blm == 14) k_pfa_hhat_big<14, kBig14><<<dim3(1), dim3(BigTile<14, kBig14>::kLanes), 0, stream>>>(f.b, bn2, f.hhat, scale, tws);
-  else PAL_SWITCH_LM(blm, k_pfa_hhat<LM><<<dim3(1), dim3(PfaLds<LM>::kLanes), 0, stream>>>(f.b, bn2, f.hhat, scale, tws));
+  Pfa& f = pl.pfa;
+  f = Pfa();
+  static_cast<PfaSplit&>(f) = pfa_split(pl.n, pl.nout, pl.inv.g, plan_sw);
+  if (!f.on()) return PAL_OK;
+  const cd* tws = stage_table(f.lm, f.lm == 11 || f.lm == 12);
+  if (!tws || !stage_table(f.lm)) return fail(PAL_ERR_NOMEM, "twiddle tables");   // (the full table feeds the register twiddles)
+  PAL_HIP(hipMalloc(&f.b, sizeof(cd) * f.n2));
+  PAL_HIP(hipMalloc(&f.hhat, sizeof(cd) << f.lm));
+  PAL_HIP(hipMalloc(&f.r1, sizeof(cd) * f.n1));
+  k_make_chirp<<<dim3((f.n2 + 255) / 256), dim3(256), 0, stream>>>(f.b, f.n2, int(f.u2));
+  k_make_roots<<<dim3((f.n1 + 255) / 256), dim3(256), 0, stream>>>(f.r1, f.n1, double(f.n1));
+  const double scale = 1.0 / (double(1 << f.lm) * double(pl.n));   // inverse FFT_M and numpy.fft.ifft's 1/n
+  if (f.lm == 13) k_pfa_hhat_big<13, kBig13><<<dim3(1), dim3(BigTile<13, kBig13>::kLanes), 0, stream>>>(f.b, f.n2, f.hhat, scale, tws);
+  else if (f.lm == 14) k_pfa_hhat_big<14, kBig14><<<dim3(1), dim3(BigTile<14, kBig14>::kLanes), 0, stream>>>(f.b, f.n2, f.hhat, scale, tws);
+  else PAL_SWITCH_LM(f.lm, k_pfa_hhat<LM><<<dim3(1), dim3(PfaLds<LM>::kLanes), 0, stream>>>(f.b, f.n2, f.hhat, scale, tws));
   PAL_HIP(hipGetLastError());
-  // cos / sin of 2 pi j t / N1 with the argument reduced exactly (j t mod N1) before the long-double evaluation
-  std::vector<double> tab(size_t(h + kPfaUnr) * f.nch * 2 * kPfaTC, 0.0);   // kPfaUnr zero rows behind the last step
-  const long double two_pi = 6.283185307179586476925286766559005768L;
-  for (int j = 1; j <= h; ++j)
-    for (int t = 1; t <= h; ++t) {
-      const int ch = (t - 1) / kPfaTC, tt = (t - 1) % kPfaTC;
-      const long double ang = two_pi * (long double)((long long)j * t % bn1) / (long double)bn1;
-      double* row = &tab[(size_t(j - 1) * f.nch + ch) * 2 * kPfaTC];
-      row[tt] = double(cosl(ang));
-      row[kPfaTC + tt] = double(sinl(ang));
-    }
-  // twiddle bookkeeping of the row pass's last stage: per row of Y the index multiplier and its step (pfa_kernels.h)
-  {
-    const int ll = stage_tw_last(blm);
-    const long long P = 1ll << ll;
-    std::vector<int2> rt;
-    rt.resize(size_t(bn1));
-    for (int row = 0; row < bn1; ++row) {
-      const long long uk = (long long)f.u1 * row % bn1;
-      rt[size_t(row)] = make_int2(int(uk), int(uk * P % bn1));
-    }
-    PAL_HIP(hipMalloc(&f.rowtab, rt.size() * sizeof(int2)));
-    PAL_HIP(hipMemcpy(f.rowtab, rt.data(), rt.size() * sizeof(int2), hipMemcpyHostToDevice));
-  }
-  PAL_HIP(hipMalloc(&f.T, tab.size() * sizeof(double)));
-  PAL_HIP(hipMemcpyAsync(f.T, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-  PAL_HIP(hipStreamSynchronize(stream));       // `tab` is host memory
-  if (allow_rader && bn2 == 991) PAL_TRY(build_rader(f, n, u2 % bn2));   // 991 is prime and 990 = 11 x 9 x 10
-  if (allow_r89 && bn1 == kR89 && f.nch == 4) {                // the 89-point column DFT as Rader's 8 x 11 convolution (pfa_rader89.h)
+  PAL_TRY(upload_table(this, pfa_row_table(f.n1, f.u1, stage_tw_last(f.lm)), &f.rowtab));
+  PAL_TRY(upload_table(this, pfa_col_table(f.n1, f.nch), &f.T));
+  if (f.rader) PAL_TRY(build_rader(f, pl.n, f.u2 % f.n2));
+  if (f.r89) {                                                 // the 89-point column DFT as Rader's 8 x 11 convolution (pfa_rader89.h)
     Rader89Tab tab;
     make_rader89_tab(tab);
-    PAL_HIP(hipMalloc(&f.r89, sizeof tab));
-    PAL_HIP(hipMemcpy(f.r89, &tab, sizeof tab, hipMemcpyHostToDevice));
+    PAL_HIP(hipMalloc(&f.r89_tab, sizeof tab));
+    PAL_HIP(hipMemcpy(f.r89_tab, &tab, sizeof tab, hipMemcpyHostToDevice));
   }
-  pl.pfa = f;
   return PAL_OK;
 }
 
-template <class T> static int upload_table(Engine* e, const std::vector<T>& host, T** dev) {
-  if (hipMalloc(dev, host.size() * sizeof(T)) != hipSuccess) return e->fail(PAL_ERR_NOMEM, "rader tables");
-  return e->check(hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice), "rader tables");
-}
-
-// Rader tables of the prime N2 = f.n2 (pfa_rader.h): generator re-indexing into prime-factor positions and the 3-D
+// Rader tables of the prime N2 = f.n2 (pfa_rader.h): generator re-indexing into prime-factor positions (mixed_radix.h) and the 3-D
 // spectra of the kernel sequences w^(g^s), w = exp(+/- 2 pi i u2 / N2)
 int Engine::build_rader(Pfa& f, long long n, long long u2) {
-  constexpr int R1 = 11, R2 = 9, R3 = 10;
-  const int p = f.n2, L = p - 1;
-  if (L != R1 * R2 * R3) return PAL_OK;
-  int g = 0;                                                   // smallest primitive root: order L, checked on L's prime factors
-  for (int c = 2; c < p && !g; ++c) {
-    bool ok = true;
-    for (int q : {2, 3, 5, 11}) {
-      long long x = 1, b = c;
-      for (int ex = L / q; ex; ex >>= 1, b = b * b % p)
-        if (ex & 1) x = x * b % p;
-      ok = ok && x != 1;
-    }
-    if (ok) g = c;
-  }
-  if (!g) return PAL_OK;
-  using AX = Axes<R1, R2, R3>;                                 // prime-factor positions of the convolution index (mixed_radix.h)
-  std::vector<int> gpow(L), qidx(p, 0), ridx(p, 0);
-  long long x = 1;
-  for (int s = 0; s < L; ++s, x = x * g % p) gpow[s] = int(x);
-  for (int s = 0; s < L; ++s) {
-    ridx[gpow[s]] = AX::pos(s);                                // X[g^s] = x[0] + C[s]
-    qidx[gpow[(L - s) % L]] = AX::pos(s);                      // a[s] = x[g^-s]
-  }
-  qidx[0] = L;                                                 // the rows of SP keep this order, bin 0 last
-  const long double two_pi = 6.283185307179586476925286766559005768L;
-  std::vector<long double> br(L), bi(L);                       // kernel sequence b[s] = w^(g^s), w = exp(2 pi i u2 / N2)
-  for (int s = 0; s < L; ++s) {
-    const long double ang = two_pi * (long double)(u2 * gpow[s] % p) / (long double)p;
-    br[s] = cosl(ang);
-    bi[s] = sinl(ang);
-  }
-  std::vector<long double> cr(L), ci(L);                       // exp(-2 pi i m / L)
-  for (int s = 0; s < L; ++s) {
-    const long double ang = -two_pi * (long double)s / (long double)L;
-    cr[s] = cosl(ang);
-    ci[s] = sinl(ang);
-  }
-  // 3-D spectrum at position k2 + R2 k3 + R2 R3 k1: sum_s b[s] exp(-2 pi i ((s mod R2) k2 / R2 + (s mod R3) k3 / R3 + (s mod R1) k1 / R1));
-  // inverse direction scaled by 1 / (L n) (the unnormalised inverse stages and numpy's 1 / n), forward direction (the
-  // conjugate sequence) by 1 / L
-  std::vector<cd> bhat(L), bhat_f(L);
-  const long double scale = 1.0L / ((long double)L * (long double)n);
-  for (int k1 = 0; k1 < R1; ++k1)
-    for (int k3 = 0; k3 < R3; ++k3)
-      for (int k2 = 0; k2 < R2; ++k2) {
-        long double ar = 0, ai = 0, fr = 0, fi = 0;
-        for (int s = 0; s < L; ++s) {
-          const int m = int(((long long)(s % R2) * k2 * (L / R2) + (long long)(s % R3) * k3 * (L / R3) + (long long)(s % R1) * k1 * (L / R1)) % L);
-          ar += br[s] * cr[m] - bi[s] * ci[m];
-          ai += br[s] * ci[m] + bi[s] * cr[m];
-          fr += br[s] * cr[m] + bi[s] * ci[m];                 // (br - i bi)(cr + i ci)
-          fi += br[s] * ci[m] - bi[s] * cr[m];
-        }
-        const size_t at = size_t(k2) + size_t(R2) * k3 + size_t(R2) * R3 * k1;
-        bhat[at] = mk(double(ar * scale), double(ai * scale));
-        bhat_f[at] = mk(double(fr / (long double)L), double(fi / (long double)L));
-      }
-  PAL_TRY(upload_table(this, bhat, &f.rd_bhat));
-  PAL_TRY(upload_table(this, bhat_f, &f.rd_bhat_f));
-  PAL_TRY(upload_table(this, qidx, &f.rd_qidx));
-  PAL_TRY(upload_table(this, ridx, &f.rd_ridx));
-  f.rader = true;
+  const RaderIndex ix = rader_index(f.n2, [](int s) { return Axes<kRaderR1, kRaderR2, kRaderR3>::pos(s); });
+  if (!ix.g) return fail(PAL_ERR_INTERNAL, "no primitive root of %d", f.n2);
+  const RaderSpectra sp = rader_spectra(f.n2, n, u2, ix.gpow);
+  PAL_TRY(upload_table(this, sp.inv, &f.rd_bhat));
+  PAL_TRY(upload_table(this, sp.fwd, &f.rd_bhat_f));
+  PAL_TRY(upload_table(this, ix.qidx, &f.rd_qidx));
+  PAL_TRY(upload_table(this, ix.ridx, &f.rd_ridx));
   return PAL_OK;
 }
 
 int Engine::pfa_rows(const Plan& pl, const cd* permuted, const int4* quads, int G, cd* Y, hipStream_t on) {
   const Pfa& f = pl.pfa;
-  const cd* tws = f.lm >= 11 ? stage_table_compact(f.lm) : stage_table(f.lm);
+  const cd* tws = stage_table(f.lm, f.lm >= 11);
   if (f.rader) {
     ProfScope ps(this, "k_pfa_rows_rader<11,9,10>", on);
     PfaRaderArgs a{permuted, quads, Y, f.rd_bhat, f.r1, f.rd_ridx, f.rowtab,
@@ -351,7 +226,7 @@ int Engine::pfa_pair_group_fused(const Plan& pl, const cd* permuted, const int4*
 #define PAL_COLS_STATS(AD, FU, NW, ST) k_pfa_cols_stats<kPfaTC, kPfaUnr, AD, FU, NW, ST><<<grid, dim3(64 * NW), 0, on>>>(Y, corr, stride, f.n1, f.n2, G, f.nch, f.T, zero_rows, a, rows)
 #define PAL_COLS_STATS_NW(AD, FU) do { if (shortcols) PAL_COLS_STATS(AD, false, 4, true); else if (nw == 2) PAL_COLS_STATS(AD, FU, 2, false); else PAL_COLS_STATS(AD, FU, 4, false); } while (0)
     if (f.r89 && full && nw == 4 && !shortcols) {
-      const Rader89Tab* tab = static_cast<const Rader89Tab*>(f.r89);
+      const Rader89Tab* tab = static_cast<const Rader89Tab*>(f.r89_tab);
       if (adaptive) k_pfa_cols_stats<kPfaTC, kPfaUnr, true, true, 4, false, true><<<grid, dim3(256), 0, on>>>(Y, corr, stride, f.n1, f.n2, G, f.nch, f.T, zero_rows, a, rows, tab);
       else k_pfa_cols_stats<kPfaTC, kPfaUnr, false, true, 4, false, true><<<grid, dim3(256), 0, on>>>(Y, corr, stride, f.n1, f.n2, G, f.nch, f.T, zero_rows, a, rows, tab);
     } else if (adaptive) { if (full) PAL_COLS_STATS_NW(true, true); else PAL_COLS_STATS_NW(true, false); }
@@ -485,7 +360,7 @@ int Engine::pfa_pair_group_fin(const Plan& pl, const cd* permuted, const int4* q
     // histograms only where fin_decide's bound on the median (from sum x^2, the maximum set apart) cannot decide: multipliers above 2 (or negative)
     const bool hist = !(a.method > 0 || fa.cheb);
     const int nw = f.nch == 2 ? 2 : (f.nch == 3 && !hist ? 3 : 4);   // (three chunks: three wavefronts where the statistics are per wavefront)
-    FinSrc src{Y, f.T, static_cast<const Rader89Tab*>(f.r89)};
+    FinSrc src{Y, f.T, static_cast<const Rader89Tab*>(f.r89_tab)};
     PAL_TRY(fin_serialize(on));
 #define PAL_COLS_FIN(MODE, HI, FU, NW) k_pfa_cols_fin<MODE, kPfaTC, kPfaUnr, HI, FU, NW><<<grid, dim3(64 * NW), 0, on>>>(src, f.n1, f.n2, G, f.nch, nblk, zero_rows, a, fa, rows)
 #define PAL_COLS_FIN_FU(MODE, HI, NW) do { if (full) PAL_COLS_FIN(MODE, HI, true, NW); else PAL_COLS_FIN(MODE, HI, false, NW); } while (0)

@@ -6,19 +6,18 @@
 #include <vector>
 
 #include "pair_route.h"
+#include "plan_geometry.h"
 
 using namespace pal;
 
 static int failures = 0;
 #define CHECK(c, ...) do { if (!(c)) { if (++failures <= 20) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } } while (0)
 
-// a plan's shape from its cut, as Engine::build_pfa fills it: chunks of 11 output indices (kPfaTC), row tiles of 2^lm >= 2 N2 - 1 points
+// a plan's shape from its cut, with the row tile and the chunks of output indices that pfa_split gives it (plan_geometry.h)
 static RouteIn split(int n1, int n2, bool r89 = false) {
-  const int h = (n1 - 1) / 2;
-  int lm = 9;
-  while ((1 << lm) < 2 * n2 - 1) ++lm;
+  const TileChunks t = pfa_tile_chunks(n1, n2);
   RouteIn f{};
-  f.n = f.nout = n1 * n2; f.split = true; f.n1 = n1; f.n2 = n2; f.nch = h > 0 ? (h + 10) / 11 : 1; f.lm = lm; f.r89 = r89;
+  f.n = f.nout = n1 * n2; f.split = true; f.n1 = n1; f.n2 = n2; f.nch = t.nch; f.lm = t.lm; f.r89 = r89;
   return f;
 }
 static RouteIn whole(int n, int nout) {

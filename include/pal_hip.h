@@ -220,6 +220,35 @@ int pal_solve_positions_loss(pal_handle h, const pal_pair_record* tables, int B,
                              const double* calib, const double* weights, const double* extra_starts, const pal_solve_params* prm,
                              pal_position_record* out, int32_t loss, double f_scale, double* pair_weights);
 
+/* ---- loop closure of TDOA tables: votes and weights (no counterpart in the reference) ------------
+ * For three microphones x < y < z the lags of a consistent table close: lag_xy + lag_yz - lag_xz = 0 up to rounding, whatever the
+ * geometry, the speed of sound or the calibration delays (calib[j] - calib[i] cancels around a triangle).  A pair whose row picked a
+ * multipath or noise peak breaks every triangle it belongs to.  Integer arithmetic on k_sel throughout (lag = k_sel - (lengths[b] - 1)):
+ * pyaudiolocalization_amd/closure.py states it index by index and the device equals it bit for bit.
+ *   tables[B][P] (P = M(M-1)/2, row-major i<j), lengths[B] (host, read before the call returns);
+ *   votes[B][P]: per pair (i, j) the number of third microphones k whose triangle with i and j closes within tol samples;
+ *   mic_closed[B][M]: closed triangles that contain microphone m (half the sum of the votes of its pairs);
+ *   weights[B][P]: PAL_CLOSURE_W_*, ready to be the weights of pal_solve_positions* under PAL_SOLVE_W_ARRAY;
+ *   summary[B].  Each of the four outputs may be NULL, not all of them.  Results do not depend on which other frames share the call.
+ * 3 <= M <= 256, B >= 1, 0 <= tol <= 2^20, min_votes >= 0 (above M - 2: every weight is 0), 1 <= lengths[b] <= 2^24, a known mode:
+ * PAL_ERR_INVALID otherwise, and for a record whose k_sel lies outside 0..2 lengths[b] - 2 (so that a sum of three lags stays far inside
+ * int32): the host form reports it itself, the _dev form - asynchronous like every _dev entry point, results complete after
+ * pal_synchronize - through pal_synchronize, like the bad row index of a device pair list.
+ * What the check cannot see: a constant clock offset of one microphone shifts all its lags consistently and closes every triangle. */
+#define PAL_CLOSURE_W_MASK 0   /* weight = votes >= min_votes ? 1 : 0                */
+#define PAL_CLOSURE_W_SOFT 1   /* weight = votes >= min_votes ? votes / (M - 2) : 0  */
+typedef struct pal_closure_frame {   /* 16 bytes */
+  int32_t closed;      /* triangles x<y<z of the frame with |lag_xy + lag_yz - lag_xz| <= tol   */
+  int32_t triangles;   /* M (M-1) (M-2) / 6                                                     */
+  int32_t kept_pairs;  /* pairs with weight > 0                                                 */
+  int32_t worst_mic;   /* argmin of mic_closed, lowest index at ties                            */
+} pal_closure_frame;
+int pal_tdoa_closure_dev(pal_handle h, const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, int32_t tol,
+                         int32_t min_votes, int32_t weight_mode, int32_t* d_votes, int32_t* d_mic_closed, double* d_weights,
+                         pal_closure_frame* d_summary);
+int pal_tdoa_closure(pal_handle h, const pal_pair_record* tables, int B, int M, const int32_t* lengths, int32_t tol, int32_t min_votes,
+                     int32_t weight_mode, int32_t* votes, int32_t* mic_closed, double* weights, pal_closure_frame* summary);
+
 /* single-pair signatures: phat_correlation(sig1, sig2) (utils.py:108) -> corr[n1+n2-1] */
 int pal_phat_correlation(pal_handle h, const double* sig1, int n1, const double* sig2, int n2, double* corr);
 /* get_time_delays_phat (utils.py:121): corr[n1+n2-1] (may be NULL), k_out[num_peaks] array indices */

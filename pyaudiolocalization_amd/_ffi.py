@@ -16,6 +16,7 @@ PAL_MAX_PEAKS = 256
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL, ERR_COMM, ERR_MATERIAL = -1, -2, -3, -4, -5, -6, -7
 BR_ALT_THRESHOLD, BR_ARGMAX_NO_PEAKS, BR_WINDOW_RETRY, BR_ARGMAX_WINDOW = 1, 2, 4, 8
 BOOT_PERMUTATION, BOOT_BLOCK, BOOT_CIRCULAR = 0, 1, 2
+CLOSURE_W_MASK, CLOSURE_W_SOFT = 0, 1
 
 
 class PhatParams(C.Structure):
@@ -81,6 +82,10 @@ SIGNATURES = {
                                                C.POINTER(SolveParams), C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
     "pal_solve_positions_loss": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(SolveParams), C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
+    "pal_tdoa_closure_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "pal_tdoa_closure": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "pal_phat_correlation": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "pal_get_time_delays_phat": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(PhatParams), C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

@@ -88,7 +88,8 @@ enum Ws : int {
   kWsSolve = 22,       // the position solve (solve.hip): uploaded small inputs, (b, w) per pair, starts, per-start results, records
   kWsBlockTable = 23,  // (caller) records in blocked pair order (all_pairs_dev, large arrays)
   kWsResample = 24,    // resample.hip: the interleaved (win, delta) filter table of the latest ratio
-  kWsCount = 25
+  kWsClosure = 25,     // the closure check (closure.hip): frame lengths, dense lag matrices, votes when the caller takes none
+  kWsCount = 26
 };
 constexpr Ws peak_scratch_slot(int slot) { return slot == 0 ? kWsPeaks0 : (slot == 1 ? kWsPeaks1 : kWsPeaks2); }
 constexpr Ws fin_scratch_slot(int slot) { return Ws(kWsFin0 + slot); }
@@ -212,6 +213,10 @@ struct Engine {
   int solve_positions_impl(const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics, const double* calib,
                            const double* weights, const double* extra_starts, const pal_solve_params* prm, pal_position_record* out,
                            int loss, double f_scale, double* pair_weights);
+  // closure.hip: loop closure of TDOA tables (d_tables and the four outputs in HBM, each output or nullptr; lengths a host array); asynchronous
+  int tdoa_closure_dev(const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, int32_t tol, int32_t min_votes, int32_t weight_mode,
+                       int32_t* d_votes, int32_t* d_mic_closed, double* d_weights, pal_closure_frame* d_summary);
+  int closure_check(int B, int M, const int32_t* lengths, int32_t tol, int32_t min_votes, int32_t weight_mode);
   int32_t* solve_idx = nullptr;    // device table pair -> i | j << 16 of the last microphone count
   int solve_idx_M = 0;
   // resample.hip: the right wing of the interpolation filter as pal_resample_set_filter received it, and the ratio whose scaled

@@ -121,6 +121,7 @@ static int check_status(Engine* e) {
   if (st[kStInput]) {                        // input problems found by device-side checks
     hipMemset(dev + kStInput, 0, sizeof(int));
     if (st[kStInput] & kStInputBadRow) return e->fail(PAL_ERR_INVALID, "pair list references a row outside the frame batch");
+    if (st[kStInput] & kStInputBadLag) return e->fail(PAL_ERR_INVALID, "a record of the TDOA table has k_sel outside 0..2 length - 2: the closure results of this call are not valid");
     return e->fail(PAL_ERR_INVALID, "non-finite sample (NaN or infinity) in a frame: the pair packed with that microphone's "
                                     "pairs would be affected too, the table of this call is not valid");
   }
@@ -556,6 +557,47 @@ int pal_solve_positions_loss(pal_handle h, const pal_pair_record* tables, int B,
   PAL_TRY(e->check(hipMemcpyAsync(dt, tables, bytes, hipMemcpyHostToDevice, e->stream), "tables upload"));
   return e->solve_positions_loss_dev(static_cast<const pal_pair_record*>(dt), B, M, lengths, mics, calib, weights, extra_starts, prm, out, loss,
                                      f_scale, pair_weights);
+}
+
+int pal_tdoa_closure_dev(pal_handle h, const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, int32_t tol, int32_t min_votes,
+                         int32_t weight_mode, int32_t* d_votes, int32_t* d_mic_closed, double* d_weights, pal_closure_frame* d_summary) {
+  ENGINE(h);
+  return e->tdoa_closure_dev(d_tables, B, M, lengths, tol, min_votes, weight_mode, d_votes, d_mic_closed, d_weights, d_summary);
+}
+
+int pal_tdoa_closure(pal_handle h, const pal_pair_record* tables, int B, int M, const int32_t* lengths, int32_t tol, int32_t min_votes,
+                     int32_t weight_mode, int32_t* votes, int32_t* mic_closed, double* weights, pal_closure_frame* summary) {
+  ENGINE(h);
+  PAL_TRY(e->closure_check(B, M, lengths, tol, min_votes, weight_mode));
+  if (!tables) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  if (!votes && !mic_closed && !weights && !summary) return e->fail(PAL_ERR_INVALID, "no output requested");
+  const size_t P = size_t(M) * size_t(M - 1) / 2, np = size_t(B) * P;
+  for (size_t r = 0; r < np; ++r) {
+    const int64_t k = tables[r].k_sel, len = lengths[r / P];
+    if (k < 0 || k > 2 * len - 2)
+      return e->fail(PAL_ERR_INVALID, "frame %d, pair %d: k_sel %d outside 0..%d", int(r / P), int(r % P), int(k), int(2 * len - 2));
+  }
+  // staged outputs in one block: [votes | mic_closed | weights | summary]
+  auto align = [](size_t v) { return (v + 255) & ~size_t(255); };
+  const size_t o_votes = 0, o_mic = align(votes ? np * sizeof(int32_t) : 0);
+  const size_t o_wt = o_mic + align(mic_closed ? size_t(B) * M * sizeof(int32_t) : 0);
+  const size_t o_sum = o_wt + align(weights ? np * sizeof(double) : 0);
+  const size_t total = o_sum + align(summary ? size_t(B) * sizeof(pal_closure_frame) : 0);
+  void* dt = nullptr;
+  char* out = nullptr;
+  PAL_TRY(e->scratch(kWsStageTable, np * sizeof(pal_pair_record), &dt));
+  PAL_TRY(e->scratch(kWsStageOut, total, &out));
+  PAL_TRY(e->check(hipMemcpyAsync(dt, tables, np * sizeof(pal_pair_record), hipMemcpyHostToDevice, e->stream), "tables upload"));
+  int32_t* dv = votes ? reinterpret_cast<int32_t*>(out + o_votes) : nullptr;
+  int32_t* dm = mic_closed ? reinterpret_cast<int32_t*>(out + o_mic) : nullptr;
+  double* dw = weights ? reinterpret_cast<double*>(out + o_wt) : nullptr;
+  pal_closure_frame* ds = summary ? reinterpret_cast<pal_closure_frame*>(out + o_sum) : nullptr;
+  PAL_TRY(e->tdoa_closure_dev(static_cast<const pal_pair_record*>(dt), B, M, lengths, tol, min_votes, weight_mode, dv, dm, dw, ds));
+  if (votes) PAL_TRY(e->check(hipMemcpyAsync(votes, dv, np * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "votes download"));
+  if (mic_closed) PAL_TRY(e->check(hipMemcpyAsync(mic_closed, dm, size_t(B) * M * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "mic_closed download"));
+  if (weights) PAL_TRY(e->check(hipMemcpyAsync(weights, dw, np * sizeof(double), hipMemcpyDeviceToHost, e->stream), "weights download"));
+  if (summary) PAL_TRY(e->check(hipMemcpyAsync(summary, ds, size_t(B) * sizeof(pal_closure_frame), hipMemcpyDeviceToHost, e->stream), "summary download"));
+  return pal_synchronize(h);
 }
 
 static int single_pair(Engine* e, const double* sig1, int n1, const double* sig2, int n2, const pal_phat_params* prm,

@@ -13,7 +13,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _ffi, bootstrap, solve
+from . import _ffi, bootstrap, closure, solve
 from ._ffi import RECORD, PalError, PhatParams, SolveParams, f64, ptr
 
 
@@ -216,7 +216,7 @@ class Engine:
         wt = None
         if isinstance(weights, str):
             if weights not in ("ones", "snr"):
-                raise ValueError("weights: 'ones', 'snr' or an array of [B][P] weights")
+                raise ValueError("weights: 'ones', 'snr', 'closure' or an array of [B][P] weights")
             mode = solve.WEIGHTS[weights]
         else:
             mode = solve.WEIGHTS["array"]
@@ -225,12 +225,57 @@ class Engine:
         prm = SolveParams(float(fs), float(c), float(buffer), int(grid), int(max_iter), mode, 0 if ex is None else ex.shape[1])
         return m, ln, mics, cal, wt, ex, prm
 
+    # ---- loop closure of TDOA tables (specification: closure.py) ---------------------------------
+    def tdoa_closure(self, tables, lengths, m: int, tol: int = 1, min_votes: int = 1, mode: str = "soft", outputs=closure.OUTPUTS):
+        """tables[B][P] (or [P]) of _ffi.RECORD, lengths[B] (or one length), m microphones -> (votes[B][P] int32, mic_closed[B][m] int32,
+        weights[B][P] float64, summary[B] of closure.SUMMARY): per pair the third microphones whose triangle closes within ``tol``
+        samples, per microphone its closed triangles, per pair the weight (``mode`` 'mask': 1 from ``min_votes`` votes, 'soft':
+        votes / (m - 2) from ``min_votes`` votes, else 0) and per frame the counts - see closure.py.  ``outputs``: the names of the
+        outputs to compute; the others come back as None."""
+        tab = np.ascontiguousarray(tables, dtype=RECORD)
+        if tab.ndim == 1:
+            tab = tab[None]
+        if tab.ndim != 2:
+            raise ValueError("tables must be [P] or [B][P]")
+        b, p = tab.shape
+        code, ln = closure.check_args(b, m, lengths, tol, min_votes, mode)
+        if p != int(m) * (int(m) - 1) // 2:
+            raise ValueError(f"a table of {int(m)} microphones has {int(m) * (int(m) - 1) // 2} rows per frame, got {p}")
+        out = closure.empty_outputs(b, int(m), outputs)
+        self._check(self._lib.pal_tdoa_closure(self._h, tab.ctypes.data, b, int(m), ln.ctypes.data, int(tol), int(min_votes), code,
+                                               *[ptr(a) for a in out]))
+        return out
+
+    def tdoa_closure_dev(self, d_tables: int, b: int, m: int, lengths, tol: int = 1, min_votes: int = 1, mode: str = "soft", d_votes: int = 0,
+                         d_mic_closed: int = 0, d_weights: int = 0, d_summary: int = 0) -> None:
+        """Asynchronous: tables[b][P] and the requested outputs (0 = not wanted; at least one) stay in HBM; ``lengths`` is read before
+        the call returns.  A record whose k_sel lies outside 0..2 length - 2 is reported by ``synchronize``."""
+        code, ln = closure.check_args(b, m, lengths, tol, min_votes, mode)
+        self._check(self._lib.pal_tdoa_closure_dev(self._h, C.c_void_p(d_tables), int(b), int(m), ln.ctypes.data, int(tol), int(min_votes), code,
+                                                   *[C.c_void_p(int(d)) if d else None for d in (d_votes, d_mic_closed, d_weights, d_summary)]))
+
+    def _closure_weights_dev(self, d_tables: int, b: int, m: int, lengths, tol, min_votes, mode) -> np.ndarray:
+        """The closure weights[b][P] of tables in HBM: only the weights come down."""
+        w = np.zeros((int(b), m * (m - 1) // 2), dtype=np.float64)
+        d_w = self.alloc(w.nbytes)
+        try:
+            self.tdoa_closure_dev(d_tables, b, m, lengths, tol, min_votes, mode, d_weights=d_w)
+            self.synchronize()
+            self.download(w, d_w)
+        finally:
+            self.free(d_w)
+        return w
+
     def solve_positions(self, tables, lengths, mic_positions, fs, c, calib_delays=None, weights="ones", buffer=5.0, grid=solve.GRID,
-                        max_iter=solve.MAX_ITER, extra_starts=None, loss="linear", f_scale=1.0, return_pair_weights=False):
+                        max_iter=solve.MAX_ITER, extra_starts=None, loss="linear", f_scale=1.0, return_pair_weights=False,
+                        closure_tol=1, closure_min_votes=1, closure_mode="soft"):
         """tables[B][P] (or [P]) of _ffi.RECORD, lengths[B] (or one length) -> records[B] of solve.POSITION.  ``weights``: 'ones',
-        'snr' (snr / mean(snr) of the records, as compute_weights) or an array [B][P]; ``extra_starts`` [B][n][3].  ``loss``: one of
+        'snr' (snr / mean(snr) of the records, as compute_weights), 'closure' or an array [B][P]; ``extra_starts`` [B][n][3].  ``loss``: one of
         solve.LOSSES, with ``f_scale`` in metres of weighted residual, for tables with outlier pairs; ``return_pair_weights``:
-        -> (records, rho'(z)[B][P] at the positions: 1 for a pair the fit kept, towards 0 for one it discounted)."""
+        -> (records, rho'(z)[B][P] at the positions: 1 for a pair the fit kept, towards 0 for one it discounted).
+        ``weights='closure'``: the weights of ``tdoa_closure(tables, lengths, M, closure_tol, closure_min_votes, closure_mode)``, computed on
+        the device, as the array.  A frame that keeps fewer than four pairs is solved like any other: its record means nothing, and
+        ``kept_pairs`` of ``tdoa_closure``'s summary is where the caller sees it."""
         code, f_scale = solve.check_loss(loss, f_scale)
         tab = np.ascontiguousarray(tables, dtype=RECORD)
         if tab.ndim == 1:
@@ -238,6 +283,9 @@ class Engine:
         if tab.ndim != 2:
             raise ValueError("tables must be [P] or [B][P]")
         b, p = tab.shape
+        if isinstance(weights, str) and weights == "closure":
+            weights = self.tdoa_closure(tab, lengths, np.asarray(mic_positions).shape[0], closure_tol, closure_min_votes, closure_mode,
+                                        outputs=("weights",))[2]
         m, ln, mics, cal, wt, ex, prm = self._solve_args(b, p, lengths, mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter,
                                                          extra_starts)
         out = np.zeros(b, dtype=solve.POSITION)
@@ -252,10 +300,14 @@ class Engine:
 
     def solve_positions_dev(self, d_tables: int, b: int, lengths, mic_positions, fs, c, calib_delays=None, weights="ones", buffer=5.0,
                             grid=solve.GRID, max_iter=solve.MAX_ITER, extra_starts=None, loss="linear", f_scale=1.0,
-                            return_pair_weights=False):
-        """The same with the tables[B][P] in HBM (e.g. where gcc_phat_all_pairs_dev wrote them); returns when the records are on the host."""
+                            return_pair_weights=False, closure_tol=1, closure_min_votes=1, closure_mode="soft"):
+        """The same with the tables[B][P] in HBM (e.g. where gcc_phat_all_pairs_dev wrote them); returns when the records are on the host.
+        ``weights='closure'``: the closure check runs on the tables where they are and only its weights come down, to go into the solve
+        as the array (a frame that keeps fewer than four pairs is solved like any other: see solve_positions)."""
         code, f_scale = solve.check_loss(loss, f_scale)
         m = np.asarray(mic_positions).shape[0]
+        if isinstance(weights, str) and weights == "closure":
+            weights = self._closure_weights_dev(d_tables, b, m, lengths, closure_tol, closure_min_votes, closure_mode)
         m, ln, mics, cal, wt, ex, prm = self._solve_args(int(b), m * (m - 1) // 2, lengths, mic_positions, fs, c, calib_delays, weights, buffer,
                                                          grid, max_iter, extra_starts)
         out = np.zeros(int(b), dtype=solve.POSITION)

@@ -158,12 +158,15 @@ def host_position(table, length, mic_positions, fs, c, calib_delays, weights, cl
 
 def solve_positions_device(tables, lengths, mic_positions, fs, c, calib_delays=None, weights=None, buffer=5.0, grid=4, max_iter=200,
                            extra_starts=None, engine=None, return_records=False, clustering=("kmeans", 0.001, 2), loss="linear",
-                           f_scale=1.0):
+                           f_scale=1.0, closure_tol=1, closure_min_votes=1, closure_mode="soft"):
     """TDOA tables[B][P] (or [P]) -> positions[B][3] by the batched device solve (Engine.solve_positions; algorithm: solve.py).
     ``weights``: None / 'ones', 'snr' (the records' SNR as compute_weights weighs it) or an array [B][P].  A frame the device does
     not solve - a weight that is not finite (an infinite SNR), or no start that ended inside a stop rule - goes through the host
     tail (solve_position) instead, as the reference would have solved it.  ``return_records``: also the solve.POSITION records.
-    ``loss`` / ``f_scale``: a robust loss of solve.LOSSES for tables with outlier pairs (the host tail knows the linear one only)."""
+    ``loss`` / ``f_scale``: a robust loss of solve.LOSSES for tables with outlier pairs (the host tail knows the linear one only).
+    ``weights='closure'``: the loop-closure weights of the tables (Engine.tdoa_closure with ``closure_tol``, ``closure_min_votes``,
+    ``closure_mode``; closure.py), computed on the device and used as the array, in the host tail too.  A frame that keeps fewer than
+    four pairs is solved like any other: its position means nothing, and ``kept_pairs`` of Engine.tdoa_closure's summary says so."""
     from . import solve as S
     S.check_loss(loss, f_scale)
     eng = engine or default_engine()
@@ -173,6 +176,8 @@ def solve_positions_device(tables, lengths, mic_positions, fs, c, calib_delays=N
         tab = tab[None]
     w = "ones" if weights is None else weights
     ln = np.broadcast_to(np.asarray(lengths, dtype=np.int64), (tab.shape[0],))
+    if isinstance(w, str) and w == "closure":
+        w = eng.tdoa_closure(tab, ln, len(mic_positions), closure_tol, closure_min_votes, closure_mode, outputs=("weights",))[2]
     robust = {} if loss == "linear" else {"loss": loss, "f_scale": f_scale}
     rec = eng.solve_positions(tab, ln, mic_positions, fs, c, calib_delays, w, buffer, grid, max_iter, extra_starts, **robust)
     pos = rec["position"].copy()

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import solve
+from . import closure, solve
 from ._ffi import RECORD
 from .engine import Engine, default_engine, make_params
 from .signal_processing import _filter_design
@@ -39,24 +39,33 @@ def position_stream(bases: Sequence[np.ndarray], delays: Sequence[np.ndarray], g
                     max_expected_delay: Optional[float] = None, engine: Optional[Engine] = None, frames_per_batch: int = 128,
                     timings: Optional[Dict[str, float]] = None, calib_delays=None, weights: str = "ones", buffer: float = 5.0,
                     grid: int = solve.GRID, max_iter: int = solve.MAX_ITER, loss: str = "linear",
-                    f_scale: float = 1.0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                    f_scale: float = 1.0, closure_tol: int = 1, closure_min_votes: int = 1,
+                    closure_mode: str = "soft") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """The chain of tdoa_stream with the position solve (solve.py) run on the table buffer while it is still in HBM:
     -> (positions[F] of solve.POSITION records, tables[F][P], lengths[F]).  Tables and lengths are tdoa_stream's; the positions are
-    what Engine.solve_positions returns for those tables (``weights``: 'ones' or 'snr'; ``loss`` / ``f_scale``: a robust loss for
-    tables with outlier pairs).  A frame without the converged bit in ``positions["status"]`` is the caller's to hand to
-    main.solve_positions_device / solve_position."""
-    args = _solve_keywords(mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter, loss, f_scale)
+    what Engine.solve_positions returns for those tables (``weights``: 'ones', 'snr' or 'closure'; ``loss`` / ``f_scale``: a robust loss for
+    tables with outlier pairs).  ``weights='closure'``: the loop-closure check (closure.py; ``closure_tol``, ``closure_min_votes``,
+    ``closure_mode``) runs on the table buffer in HBM and only its weights come down, to go into the solve as an array; a frame that
+    keeps fewer than four pairs is solved like any other and its record means nothing (Engine.tdoa_closure's ``kept_pairs`` tells).
+    A frame without the converged bit in ``positions["status"]`` is the caller's to hand to main.solve_positions_device / solve_position."""
+    args = _solve_keywords(mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter, loss, f_scale, closure_tol, closure_min_votes,
+                           closure_mode)
     tables, lengths, positions = _chain(bases, delays, gains, fs, totals, trim_len, filter_method, max_expected_delay, engine,
                                         frames_per_batch, timings, args)
     return positions, tables, lengths
 
 
-def _solve_keywords(mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter, loss, f_scale):
-    """Keywords of Engine.solve_positions_dev for a stream, checked before any GPU work; the linear loss passes none of its own."""
-    if weights not in ("ones", "snr"):
-        raise ValueError("weights: 'ones' or 'snr'")
+def _solve_keywords(mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter, loss, f_scale, closure_tol=1, closure_min_votes=1,
+                    closure_mode="soft"):
+    """Keywords of Engine.solve_positions_dev for a stream, checked before any GPU work; the linear loss passes none of its own, and
+    only the closure weights pass theirs."""
+    if not isinstance(weights, str) or weights not in ("ones", "snr", "closure"):
+        raise ValueError("weights: 'ones', 'snr' or 'closure'")
     solve.check_loss(loss, f_scale)
     args = dict(mic_positions=mic_positions, fs=fs, c=c, calib_delays=calib_delays, weights=weights, buffer=buffer, grid=grid, max_iter=max_iter)
+    if weights == "closure":
+        closure.check_args(1, np.asarray(mic_positions).shape[0], 1, closure_tol, closure_min_votes, closure_mode)
+        args.update(closure_tol=closure_tol, closure_min_votes=closure_min_votes, closure_mode=closure_mode)
     if loss != "linear":
         args.update(loss=loss, f_scale=f_scale)
     return args
@@ -326,10 +335,13 @@ def recorded_position_stream(recordings, fs_in: float, fs: float, frame_len: int
                              engine: Optional[Engine] = None, frames_per_batch: int = 128, timings: Optional[Dict[str, float]] = None,
                              calib_delays=None, weights: str = "ones", buffer: float = 5.0, grid: int = solve.GRID,
                              max_iter: int = solve.MAX_ITER, loss: str = "linear",
-                             f_scale: float = 1.0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                             f_scale: float = 1.0, closure_tol: int = 1, closure_min_votes: int = 1,
+                             closure_mode: str = "soft") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """recorded_tdoa_stream with the position solve of position_stream on each batch's tables while they are in HBM:
-    -> (positions[F] of solve.POSITION records, tables[F][P], lengths[F])."""
-    args = _solve_keywords(mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter, loss, f_scale)
+    -> (positions[F] of solve.POSITION records, tables[F][P], lengths[F]).  ``weights='closure'`` and its keywords: as position_stream
+    (a frame that keeps fewer than four pairs is solved like any other and its record means nothing)."""
+    args = _solve_keywords(mic_positions, fs, c, calib_delays, weights, buffer, grid, max_iter, loss, f_scale, closure_tol, closure_min_votes,
+                           closure_mode)
     tables, lengths, positions = _recorded(recordings, fs_in, fs, frame_len, hop, filter_method, max_expected_delay, engine,
                                            frames_per_batch, timings, args)
     return positions, tables, lengths

@@ -8,10 +8,10 @@ import pytest
 from oracle import cases
 from oracle import pal_oracle as O
 from pyaudiolocalization_amd import bootstrap as B
-from pyaudiolocalization_amd import synthetic
 from pyaudiolocalization_amd.engine import pair_list
 
 import stages
+from bootstrap_shapes import frame as _frame, oracle_peaks as _oracle_peaks
 
 pytestmark = pytest.mark.gpu
 
@@ -25,20 +25,6 @@ def _engine(engine):
     E._default = engine
     yield
     E._default = None
-
-
-def _frame(mics, L):
-    return synthetic.metric_frames(1, mics, L)[0]
-
-
-def _oracle_peaks(rows, pairs, S, mode, block_size, seed):
-    L = rows.shape[1]
-    out = np.empty((len(pairs), S))
-    for p, (i, j) in enumerate(pairs):
-        for s in range(S):
-            perm = B.shuffle_indices(L, i, j, s, mode, block_size, seed)
-            out[p, s] = np.max(O.phat_correlation(rows[i], rows[j][perm]))
-    return out
 
 
 @pytest.mark.parametrize("L", [1801, 44100])          # a prime length, and the prime-factor route's 44 100

@@ -89,10 +89,12 @@ enum Ws : int {
   kWsBlockTable = 23,  // (caller) records in blocked pair order (all_pairs_dev, large arrays)
   kWsResample = 24,    // resample.hip: the interleaved (win, delta) filter table of the latest ratio
   kWsClosure = 25,     // the closure check (closure.hip): frame lengths, dense lag matrices, votes when the caller takes none
-  kWsCount = 26
+  kWsFinStrip0 = 26, kWsFinStrip1 = 27, kWsFinStrip2 = 28,   // its SNR strips (pair_route.h fin_strip) per stream slot, see fin_strip_slot
+  kWsCount = 29
 };
 constexpr Ws peak_scratch_slot(int slot) { return slot == 0 ? kWsPeaks0 : (slot == 1 ? kWsPeaks1 : kWsPeaks2); }
 constexpr Ws fin_scratch_slot(int slot) { return Ws(kWsFin0 + slot); }
+constexpr Ws fin_strip_slot(int slot) { return Ws(kWsFinStrip0 + slot); }
 
 struct Engine {
   int device = 0;
@@ -250,6 +252,7 @@ struct Engine {
   unsigned fin_epoch[3] = {};   // launches of the finishing column pass per stream slot (pfa_cols_fin.h: validity tag of what its blocks exchange)
   FinKey fin_key[3];            // the layout of the slot's latest launch (fin_scratch.h: another one zeroes the block)
   unsigned fin_wrap = kFinEpochWrap;   // PAL_DEBUG_FIN_WRAP=<n>: the epoch bound (tests of the reset at the wrap)
+  bool fin_strip_on = true;     // PAL_FIN_STRIP=0: windowed calls keep the polling form of the per-wavefront statistics (pair_route.h fin_strip)
   int fin_giveup = 0;           // PAL_DEBUG_FIN_GIVEUP=1: every bounded wait of the pass gives up at once (tests of the stored-row repair)
   bool fuse_peaks = true;     // PAL_FUSED=0: separate column pass + pivot / stream launches instead of the fused column pass +
                               // peak statistics (pfa_cols_stats.h) where that applies

@@ -77,4 +77,91 @@ inline PairRoute pair_route(const RouteIn& f) {
   return {tr, lean ? RouteStats::kRowsLean : RouteStats::kThreeLaunches};
 }
 
+
+// ---- the SNR strip of the finishing pass (pfa_fin_lean.h, strip form).  A windowed call says where a row's argmax can be expected,
+// so the samples its SNR window [imax - snr_w, imax + snr_w) may need are known before the launch: the wavefronts store them to a
+// strip of the scratch, nobody waits for the row's argmax in the middle of the pass, and the finishing wavefront sums the window from
+// the strip (a row whose argmax lies elsewhere has its window evaluated from the grid by the definition of the column transform).
+// Up to three pieces, with D the window's half width in samples (the lag max_expected_delay):
+//     the row's ends   [0, D + snr_w - 1] and [n - D - snr_w, n - 1]: the rows are circular correlations as the inverse transform
+//                      leaves them - lag 0 is index 0, a delay of +d samples is index d, of -d samples index n - d.  A source whose
+//                      delay the caller's bound allows has its maximum HERE (every row of the metric run does:
+//                      tests/golden/metric_44k1_first24.npz), not inside the lag window that the selection searches;
+//     the centre       [win_lo - snr_w, win_hi + snr_w - 1]: a row whose maximum is the lag window's own best sample.
+// Pieces that touch are merged; all are clipped to the row.
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define PAL_ROUTE_HD __host__ __device__
+#else
+#define PAL_ROUTE_HD
+#endif
+
+// The strip pays while it is a small share of the row: every sample of it is one more device-scope store per row, and the wait it
+// replaces is a fixed cost per wavefront.  Measured on the metric run, strip form against PAL_FIN_STRIP=0 at the same lag window,
+// lines alternating (profiles/fin_strip_runs.txt; M pairs/s, lowest - highest): share 14 % (max_expected_delay 0.05 s) 1.750 - 1.773
+// against 1.656 - 1.694, 24 % (0.10 s) 1.703 - 1.709 against 1.620 - 1.640, 34 % (0.15 s) 1.667 - 1.669 against 1.633 - 1.646, 64 %
+// (0.30 s) 1.558 - 1.568 against 1.618 - 1.631: the largest share at which the strip form still won
+constexpr double kFinStripShare = 0.34;
+constexpr int kFinStripPieces = 3;
+
+struct FinStrip {                   // plain data: travels to the kernels inside FinArgs
+  int pieces;                       // 0: no strip (the polling form)
+  int lo[kFinStripPieces], hi[kFinStripPieces];   // [lo, hi] sample indices, ascending and disjoint; unused pieces are empty (lo 1, hi 0)
+  int base[kFinStripPieces];        // offset of lo[p] inside the strip
+  int len;                          // samples per row of the strip
+  bool on() const { return pieces > 0; }
+};
+
+inline FinStrip fin_no_strip() {
+  FinStrip s;
+  s.pieces = 0;
+  s.len = 0;
+  for (int p = 0; p < kFinStripPieces; ++p) { s.lo[p] = 1; s.hi[p] = 0; s.base[p] = 0; }
+  return s;
+}
+
+// `lean_finish`: the route is kFinish with the per-wavefront statistics (no histogram body, rows not stored); `enabled`: PAL_FIN_STRIP
+inline FinStrip fin_strip(int n, bool windowed, int win_lo, int win_hi, int snr_w, bool lean_finish, bool enabled) {
+  FinStrip s = fin_no_strip();
+  if (!enabled || !lean_finish || !windowed || win_lo > win_hi || n < 1 || snr_w < 1) return s;
+  const long long D = ((long long)win_hi - win_lo + 1) / 2;   // (the window [c - D, c + D]; clipped at the row's ends it is most of the row anyway)
+  long long lo[3] = {0, (long long)win_lo - snr_w, (long long)n - D - snr_w};
+  long long hi[3] = {D + snr_w - 1, (long long)win_hi + snr_w - 1, (long long)n - 1};
+  long long total = 0;
+  for (int p = 0; p < 3; ++p) {
+    if (lo[p] < 0) lo[p] = 0;
+    if (hi[p] > n - 1) hi[p] = n - 1;
+    if (s.pieces > 0 && lo[p] <= (long long)s.hi[s.pieces - 1] + 1) {          // touches the piece before it: one piece
+      if (hi[p] > s.hi[s.pieces - 1]) { total += hi[p] - s.hi[s.pieces - 1]; s.hi[s.pieces - 1] = int(hi[p]); }
+      continue;
+    }
+    s.lo[s.pieces] = int(lo[p]);
+    s.hi[s.pieces] = int(hi[p]);
+    s.base[s.pieces] = int(total);
+    total += hi[p] - lo[p] + 1;
+    ++s.pieces;
+  }
+  if (double(total) > kFinStripShare * double(n)) return fin_no_strip();
+  s.len = int(total);
+  return s;
+}
+
+// offset of sample m inside the strip, -1 where the strip does not hold it (the wavefronts store exactly the samples with an offset)
+PAL_ROUTE_HD inline int fin_strip_offset(const FinStrip& s, int m) {
+  int off = -1;
+  for (int p = 0; p < kFinStripPieces; ++p) off = m >= s.lo[p] && m <= s.hi[p] ? s.base[p] + (m - s.lo[p]) : off;
+  return off;
+}
+// the finisher's rule: the SNR window [lo, hi) is summed from the strip iff ONE piece holds all of it (its samples are then
+// consecutive in the strip, from the offset returned; -1: evaluate it from the grid) - a matter of the row's argmax alone, never of timing
+PAL_ROUTE_HD inline int fin_strip_window(const FinStrip& s, int lo, int hi) {
+  int off = -1;
+  for (int p = 0; p < kFinStripPieces; ++p) off = lo < hi && lo >= s.lo[p] && hi - 1 <= s.hi[p] ? s.base[p] + (lo - s.lo[p]) : off;
+  return off;
+}
+// the SNR window around a row's argmax (utils.py:238-250), [lo, hi)
+PAL_ROUTE_HD inline void fin_snr_window(int imax, int snr_w, int n, int& lo, int& hi) {
+  lo = imax - snr_w > 0 ? imax - snr_w : 0;
+  hi = imax + snr_w < n ? imax + snr_w : n;
+}
+
 }  // namespace pal

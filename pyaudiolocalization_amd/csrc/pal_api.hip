@@ -330,6 +330,8 @@ int pal_create(int device, pal_handle* out) {
   if (env) e->debug_memo = atoi(env);
   env = getenv("PAL_DEBUG_FIN_WRAP");
   if (env && atoi(env) >= 2) e->fin_wrap = unsigned(atoi(env));
+  env = getenv("PAL_FIN_STRIP");
+  if (env) e->fin_strip_on = atoi(env) != 0;
   env = getenv("PAL_DEBUG_FIN_GIVEUP");
   if (env) e->fin_giveup = atoi(env) != 0 ? 1 : 0;
   env = getenv("PAL_MAX_PLANS");

@@ -294,6 +294,11 @@ int Engine::fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, const p
   fa.corr = nullptr;
   fa.stride = 0;
   fa.store_rows = 0;
+  fa.strip = nullptr;                                          // (the strip form is pfa_pair_group_fin's choice)
+  fa.st = fin_no_strip();
+  fa.grid = nullptr;
+  fa.roots = nullptr;
+  fa.zero_rows = nullptr;
   fa.windowed = std::isnan(prm.max_expected_delay) ? 0 : 1;
   fa.win_lo = 1;
   fa.win_hi = n - 2;
@@ -361,8 +366,23 @@ int Engine::pfa_pair_group_fin(const Plan& pl, const cd* permuted, const int4* q
     const bool hist = !(a.method > 0 || fa.cheb);
     const int nw = f.nch == 2 ? 2 : (f.nch == 3 && !hist ? 3 : 4);   // (three chunks: three wavefronts where the statistics are per wavefront)
     FinSrc src{Y, f.T, static_cast<const Rader89Tab*>(f.r89_tab)};
+    // Strip form of the per-wavefront statistics (pair_route.h fin_strip): one strip buffer per launch-group slot, [2 x pair_group(n)]
+    // [strip_len] doubles.  It is written in full by every launch that reads it and read only behind that launch's `done` words, so it
+    // carries no epoch, is never zeroed and has no place in FinKey.
+    const FinStrip st = fin_strip(pl.n, fa.windowed != 0, fa.win_lo, fa.win_hi, a.snr_w, !corr && !hist, fin_strip_on);
+    if (st.on()) {
+      PAL_TRY(scratch(fin_strip_slot(slot), size_t(2 * pair_group(pl.n)) * size_t(st.len) * sizeof(double), &fa.strip));
+      fa.st = st;
+      fa.grid = Y;
+      fa.roots = f.r1;
+      fa.zero_rows = zero_rows;
+    }
+    const bool strip = fa.strip != nullptr;
     PAL_TRY(fin_serialize(on));
-#define PAL_COLS_FIN(MODE, HI, FU, NW) k_pfa_cols_fin<MODE, kPfaTC, kPfaUnr, HI, FU, NW><<<grid, dim3(64 * NW), 0, on>>>(src, f.n1, f.n2, G, f.nch, nblk, zero_rows, a, fa, rows)
+    // (HI = false: the per-wavefront statistics, in the polling or the strip form)
+#define PAL_COLS_FIN(MODE, HI, FU, NW) do { \
+      if (!HI && strip) k_pfa_cols_fin<MODE, kPfaTC, kPfaUnr, HI, FU, NW, !HI><<<grid, dim3(64 * NW), 0, on>>>(src, f.n1, f.n2, G, f.nch, nblk, zero_rows, a, fa, rows); \
+      else k_pfa_cols_fin<MODE, kPfaTC, kPfaUnr, HI, FU, NW, false><<<grid, dim3(64 * NW), 0, on>>>(src, f.n1, f.n2, G, f.nch, nblk, zero_rows, a, fa, rows); } while (0)
 #define PAL_COLS_FIN_FU(MODE, HI, NW) do { if (full) PAL_COLS_FIN(MODE, HI, true, NW); else PAL_COLS_FIN(MODE, HI, false, NW); } while (0)
     if (!hist) fa.pw = shortcols ? 4 : nw;                    // one FinPartial / `done` word per wavefront (pfa_fin_lean.h)
     if (shortcols) { if (hist) PAL_COLS_FIN(kColsStrips, true, false, 4); else PAL_COLS_FIN(kColsStrips, false, false, 4); }

@@ -41,6 +41,7 @@
 #include <climits>
 
 #include "fin_scratch.h"
+#include "pair_route.h"
 #include "pfa_cols_stats.h"
 #include "reduce.h"
 #include "wave_reduce.h"
@@ -74,6 +75,14 @@ struct FinArgs {
   size_t stride;                  //   has no finishing form): nobody polls siblings then, the finisher reads the SNR window from the stored row
   int store_rows;                 // 1: this pass writes the rows (column forms); 0 with corr set: they are there already (k_rows_lean reads them)
   int cheb;                       // 1: no histograms - the median of |corr| is bounded through sum(corr^2) (see fin_decide)
+  // strip form of the per-wavefront statistics (pair_route.h fin_strip; null: the polling form).  The wavefronts store their samples of
+  // the strip's pieces here and the finishing wavefront sums the SNR window from them.  Every entry of a launch's rows is written
+  // by that launch, and read only behind its `done` words: no epoch, no zeroing, no place in FinKey.
+  double* strip;                  // [rows][st.len]
+  FinStrip st;
+  const cd* grid;                 // the launch group's prime-factor grid [G][N1][N2], the column roots exp(-2 pi i q / N1) and the silent-row
+  const cd* roots;                //   flags: a row whose SNR window leaves the strip has it evaluated from the grid by the finishing
+  const int* zero_rows;           //   wavefront (fin_window_direct)
 };
 
 struct FinWave {                  // one wavefront's share of the finishing block's merge
@@ -440,12 +449,14 @@ struct FinSrc {
 // take nblk consecutive slots each (siblings adjacent, one XCD's L2 behind them when G is a multiple of 8)
 // HIST: threshold method 'median' with a histogram window per block (a rigorous 0.5 % interval for the row's median); false:
 //       'adaptive', or 'median' bounded without histograms (FinArgs.cheb: multipliers up to 2)
-template <int MODE, int TC, int UNR, bool HIST, bool FULL, int NW>
+// STRIP: the strip form of the per-wavefront statistics (FinArgs.strip set; pfa_fin_lean.h) - no wavefront polls its siblings
+template <int MODE, int TC, int UNR, bool HIST, bool FULL, int NW, bool STRIP = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE == kColsRader89 ? 3 : 2))) void k_pfa_cols_fin(FinSrc src, int N1, int N2, int G, int nch, int nblk,
                                                       const int* __restrict__ zero_rows, PeakArgs pa, FinArgs fa, int rows) {
   constexpr bool R89 = MODE == kColsRader89, STRIPS = MODE == kColsStrips;
   static_assert(!R89 || (NW == 4 && FULL), "the Rader column transform is the four-wavefront N1 = 89 case");
   static_assert(!HIST || NW <= 4, "the histogram form merges at most four wavefronts per block");
+  static_assert(!(HIST && STRIP), "the strip form belongs to the per-wavefront statistics");
   const cd* __restrict__ Y = src.Y;
   const double* __restrict__ T = src.T;
   const Rader89Tab* __restrict__ tab = src.tab;
@@ -519,7 +530,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
     // every wavefront on its own from here (pfa_fin_lean.h); ONE wavefront of the transform's last block then finishes both rows
     bool last;
     if constexpr (R89) {
-      last = fin_lean_r89<true, false, kR89Slots>(ro, c0, slot_t, 0u, wave, lane, g, cb, nblk, N1, N2, rows, c_lo, m2, own, inner, cb == 0 || cb == nblk - 1,
+      last = fin_lean_r89<true, false, kR89Slots, STRIP>(ro, c0, slot_t, 0u, wave, lane, g, cb, nblk, N1, N2, rows, c_lo, m2, own, inner, cb == 0 || cb == nblk - 1,
                                                   -1, true, pa, fa);
     } else {
       // dense column DFT: the accumulators become samples once (slot 1 + tt: t = ch TC + tt + 1, slot 1 + TC + tt: N1 - t; slot 0: t = 0)
@@ -535,12 +546,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
       }
       const int tl = ch * TC + (lane < TCD ? lane : lane - TCD) + 1;
       const int st = lane < TCD ? tl : N1 - tl;
-      last = fin_lean_r89<false, false, kR89Slots>(zs, z0, st, emask, wave, lane, g, cb, nblk, N1, N2, rows, c_lo, m2, own, inner,
+      last = fin_lean_r89<false, false, kR89Slots, STRIP>(zs, z0, st, emask, wave, lane, g, cb, nblk, N1, N2, rows, c_lo, m2, own, inner,
                                                    active && (c_lo == 0 || c_hi == N2), -1, true, pa, fa);
     }
     if (!last) return;
     if (wave != 0) return;                                     // ONE wavefront finishes the transform's rows (fin_row_wave)
-    fin_rows_wave(pa, fa, g, nblk, rows, N1, N2, lane);
+    fin_rows_wave<STRIP>(pa, fa, g, nblk, rows, N1, N2, lane);
     return;
   }
   // the samples of this lane, fn(value, t, exists): `value()` yields the sample (formed by two additions in the dense form, so

@@ -14,8 +14,15 @@
 //     readlane when a single lane holds one, a reduction only when several do;
 //   * the slots whose output index meets the lag window or the SNR window are a bit mask (one ballot over the lanes that
 //     hold the slot table): a slot outside costs a scalar bit test;
-//   * every wavefront polls the siblings' maxima itself and publishes its own FinPartial and `done` word
-//     (FinArgs.pw = 4 entries per block): the block's wavefronts never wait for each other after the transform.
+//   * every wavefront publishes its own FinPartial and `done` word (FinArgs.pw = 4 entries per block): the block's wavefronts
+//     never wait for each other after the transform;
+//   * the SNR window around the ROW's argmax, two compile-time forms.  Strip form (windowed calls, pair_route.h fin_strip): the
+//     wavefront stores its samples of the strip - the row's two ends, where delays of up to max_expected_delay put the maximum of
+//     a circular correlation, and the piece around the lag window - and waits for nobody; the finishing wavefront, which knows the
+//     argmax behind its `done` wait, sums the window from the strip, or evaluates it from the grid when the argmax lies where the
+//     call said it would not (fin_window_direct).  Polling form (no lag window, a strip above kFinStripShare of the row,
+//     PAL_FIN_STRIP=0): the wavefront polls the siblings' maxima and sums its own samples inside the window - a wait of about
+//     3000 of its 13 350 wave cycles on the metric run (profiles/r03_c_fin_ablation.txt), which is what the strip form removes.
 //
 // Semantics are those of pfa_cols_fin.h's general path with per-wavefront instead of per-block search floors (a floor only
 // prunes the candidate search; a wavefront whose bounded search finds no strict peak searches all its samples).
@@ -115,12 +122,16 @@ __device__ __forceinline__ double wave_pair_min(double a, double b) { return wav
 // PART (k_rows_lean's chunks of a stored row, sample m = N2 t + m2 < n): the row ends inside slot `pslot` - its samples are valid
 // where `pvalid` (the others hold zeros, which the sums may see but maxima, minima and the index search must not), later slots do
 // not exist.
-template <bool ALL, bool PART, int NS>
+// STRIP (pair_route.h fin_strip; never with PART or a stored row): the wavefront stores its samples of the strip's pieces (fa.st) and
+// leaves - no poll of the siblings' maxima, no window sums (FinPartial.w1 / w2 stay zero): the finishing wavefront sums the SNR window
+// from the strip.
+template <bool ALL, bool PART, int NS, bool STRIP = false>
 __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, const int slot_t, const unsigned emask, const int wave, const int lane,
                                              const int g, const int cb, const int nblk, const int N1, const int N2, const int rows, const int c_lo,
                                              const int m2, const bool own, const bool inner, const bool edge_block, const int pslot, const bool pvalid,
                                              const PeakArgs& pa, const FinArgs& fa) {
   static_assert(NS + 1 <= 32, "slot masks are 32 bits");
+  static_assert(!(STRIP && PART), "row chunks read stored rows: their finisher reads the SNR window from the row");
   const int n = pa.n, S = pa.splits, PW = fa.pw;
   const unsigned long long pvm = PART ? __ballot(pvalid) : ~0ull;
   const unsigned long long ownm = __ballot(own), innerm = __ballot(inner);
@@ -274,8 +285,29 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
     }
   }
 
+  // ---- strip form: the samples of the strip go out as they are (silent rows: their exact zeros), device-scope stores like the edge
+  //      columns'; stores_done() and the `done` word below order them before the finishing wavefront's loads
+  if constexpr (STRIP) {
+    unsigned smask = 0;                                        // slots whose output index meets a piece of the strip
+#pragma unroll
+    for (int p = 0; p < kFinStripPieces; ++p)
+      if (p < fa.st.pieces) smask |= slot_mask(fa.st.lo[p] / N2, fa.st.hi[p] / N2);   // (uniform)
+    if (smask) {                                               // (uniform)
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        if (r >= nrow) continue;
+        double* const dst = fa.strip + size_t(2 * g + r) * fa.st.len;
+        for_slots(r, [&](double x, int slot) {
+          if (!(smask >> slot & 1u)) return;                   // (uniform)
+          const int off = fin_strip_offset(fa.st, m2 + N2 * T(slot));
+          if (own && off >= 0) st_agent(dst + off, x);
+        });
+      }
+    }
+  }
+
   // ---- the lanes' sums and minima, once: rows 2 g and 2 g + 1 share a butterfly (even lanes end with row 2 g's total, odd
-  //      lanes with the other row's).  They stand HERE so that the siblings' maxima have more time to arrive
+  //      lanes with the other row's).  They stand HERE so that the siblings' maxima have more time to arrive (polling form)
   const double rmin = wave_pair_min(vn[0], vn[1]);
   const double r1 = wave_pair_sum(s1[0], s1[1]), r2 = wave_pair_sum(s2[0], s2[1]), ra = wave_pair_sum(a1[0], a1[1]);
 
@@ -285,7 +317,7 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
   bool have_w[2] = {false, false};
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
-    if (r >= nrow || stored) continue;                         // (uniform)
+    if (STRIP || r >= nrow || stored) continue;                // (uniform; strip form: none of this exists)
     const int row = 2 * g + r;
     double bv = -INFINITY;
     int bi = -1;
@@ -330,7 +362,7 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
   // ---- the window sums' butterfly; lane r publishes row r's results, then the wavefront's `done` word follows
   {
     double q1 = 0, q2 = 0;
-    if (have_w[0] || have_w[1]) { q1 = wave_pair_sum(w1[0], w1[1]); q2 = wave_pair_sum(w2[0], w2[1]); }   // (uniform)
+    if (!STRIP && (have_w[0] || have_w[1])) { q1 = wave_pair_sum(w1[0], w1[1]); q2 = wave_pair_sum(w2[0], w2[1]); }   // (uniform)
     if (lane < nrow) {
       FinPartial o;
       const bool second = lane == 1;
@@ -348,8 +380,37 @@ __device__ __forceinline__ bool fin_lean_r89(const cd (&ro)[NS], const cd c0, co
 }
 
 
+// ---- strip form, a row whose argmax lies where the caller's lag window said it could not: the samples of its SNR window [lo, hi) by
+//      the definition of the column transform, whatever form computed it,
+//          c[m2 + N2 t] = sum_j Y[j][m2] w^(j t),   w = exp(+2 pi i / N1)   (real part: row 2 g, imaginary part: row 2 g + 1),
+//      from the grid, which stays in the slot's workspace for the whole launch.  Lanes over consecutive samples; N1 loads and 2 N1
+//      multiply-adds per sample: slow by design, these rows are the exception.  Sums per lane (sum x, sum x^2) are added to u1, u2
+__device__ __forceinline__ void fin_window_direct(const FinArgs& fa, int row, int N1, int N2, int lo, int hi, int lane, double& u1, double& u2) {
+  const cd* const Yg = fa.grid + size_t(row >> 1) * N1 * N2;
+  const bool imag = row & 1;
+  const double keep = fa.zero_rows && fa.zero_rows[row] ? 0.0 : 1.0;    // (a silent microphone's rows are exact zeros)
+#pragma nounroll
+  for (int k = lo + lane; k < hi; k += 64) {
+    const int t = k / N2;
+    const cd* col = Yg + (k - t * N2);
+    double acc = 0;
+    int q = 0;                                                 // j t mod N1
+#pragma unroll 8
+    for (int j = 0; j < N1; ++j) {
+      const cd y = col[size_t(j) * N2], w = fa.roots[q];       // (w^q is the conjugate of the table's entry)
+      acc = imag ? __builtin_fma(y.y, w.x, __builtin_fma(-y.x, w.y, acc)) : __builtin_fma(y.x, w.x, __builtin_fma(y.y, w.y, acc));
+      q += t;
+      q = q >= N1 ? q - N1 : q;
+    }
+    const double x = acc * keep;
+    u1 += x;
+    u2 = __builtin_fma(x, x, u2);
+  }
+}
+
 // ---- the finishing WAVEFRONT: one row from the wavefronts' published results (64 lanes, uniform control flow; the counterpart of
 //      pfa_cols_fin.h fin_row for FinArgs.pw = 4 and no histograms - the same fin_decide behind its own merge across the lanes) ----
+template <bool STRIP>
 __device__ __forceinline__ void fin_row_wave(const PeakArgs& pa, const FinArgs& fa, int row, int N1, int N2, int lane) {
   const int S = pa.splits, n = pa.n, P = S * fa.pw;
   const bool windowed = fa.windowed != 0;
@@ -425,11 +486,30 @@ __device__ __forceinline__ void fin_row_wave(const PeakArgs& pa, const FinArgs& 
     s.w1 = wave_bcast63(wave_sum63(u1));
     s.w2 = wave_bcast63(wave_sum63(u2));
   }
+  if constexpr (STRIP) {                                       // strip form: the SNR window from the strip the transform's wavefronts stored ...
+    int lo, hi;
+    fin_snr_window(s.imax, pa.snr_w, n, lo, hi);
+    double u1 = 0, u2 = 0;
+    const int off = fin_strip_window(fa.st, lo, hi);
+    if (off >= 0) {                                            // (uniform, and a matter of the row's argmax alone)
+      const double* sp = fa.strip + size_t(row) * fa.st.len + off;
+      for (int k = lane; k < hi - lo; k += 64) {
+        const double x = ld_agent(sp + k);
+        u1 += x;
+        u2 = __builtin_fma(x, x, u2);
+      }
+    } else {                                                   // ... or, the argmax outside the caller's lag window, from the grid
+      fin_window_direct(fa, row, N1, N2, lo, hi, lane, u1, u2);
+    }
+    s.w1 = wave_bcast63(wave_sum63(u1));
+    s.w2 = wave_bcast63(wave_sum63(u2));
+  }
   fin_decide(pa, fa, row, s, flag, why, false, 0, 0, lane == 0);
 }
 
 // ---- the tail of a per-wavefront pass, in wavefront 0 of the transform's last block: wait for every wavefront's `done` word, then
 //      finish rows 2 g and 2 g + 1.  When the siblings' results are not there in time both rows go through the stored-row path instead
+template <bool STRIP = false>
 __device__ __forceinline__ void fin_rows_wave(const PeakArgs& pa, const FinArgs& fa, int g, int nblk, int rows, int N1, int N2, int lane) {
   bool late = fa.giveup != 0;                                  // (PAL_DEBUG_FIN_GIVEUP=1: no polls, both rows flagged)
   for (int q = lane; !fa.giveup && q < nblk * fa.pw; q += 64) {
@@ -445,7 +525,7 @@ __device__ __forceinline__ void fin_rows_wave(const PeakArgs& pa, const FinArgs&
   }
 #pragma nounroll
   for (int r = 0; r < 2; ++r)
-    if (2 * g + r < rows) fin_row_wave(pa, fa, 2 * g + r, N1, N2, lane);
+    if (2 * g + r < rows) fin_row_wave<STRIP>(pa, fa, 2 * g + r, N1, N2, lane);
 }
 
 }  // namespace pal

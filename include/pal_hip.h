@@ -135,6 +135,20 @@ int pal_gcc_phat_pairs(pal_handle h, const double* rows, int R, int L, const int
 int pal_gcc_phat_pairs_dev(pal_handle h, const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P,
                            const pal_phat_params* prm, pal_pair_record* d_table);
 
+/* The batched calls with K = prm->num_peaks (1 .. PAL_MAX_CANDIDATES = 8) selected peaks per pair instead of one: table[..] as above (the
+ * records are those of the first peak, n_sel says how many were selected), and
+ *   cand_k[..][P][K] int32: the selected array indices in the selection's order (highest peak first), -1 past n_sel;
+ *   cand_h[..][P][K] float64 (may be NULL): corr at those indices, +0.0 past n_sel.
+ * A row that ends in an argmax fallback has one candidate.  These are the inputs of pal_tdoa_consensus* below.  The 256-wide selection
+ * rows of a launch group stay in engine scratch; a small kernel compacts them into the caller's K columns.  Such a call keeps off the
+ * one-peak finishing passes (it stores its rows), so it is slower than its one-peak namesake: DESIGN 6f has the figures. */
+int pal_gcc_phat_all_pairs_peaks(pal_handle h, const double* frames, int B, int M, int L, const pal_phat_params* prm,
+                                 pal_pair_record* table, int32_t* cand_k, double* cand_h);
+int pal_gcc_phat_all_pairs_peaks_dev(pal_handle h, const double* d_frames, int B, int M, int L, const pal_phat_params* prm,
+                                     pal_pair_record* d_table, int32_t* d_cand_k, double* d_cand_h);
+int pal_gcc_phat_pairs_peaks_dev(pal_handle h, const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P,
+                                 const pal_phat_params* prm, pal_pair_record* d_table, int32_t* d_cand_k, double* d_cand_h);
+
 /* ---- bootstrap significance (utils.py:183-216) on the device -------------------------------
  * The reference shuffles sig2 = row j from NumPy's global RNG 1000 times per pair and keeps the (1 - alpha) percentile of
  * max(PHAT(sig1, shuffled sig2)).  Here shuffle s of pair (i, j) is a pure function of (seed, i, j, s, L, mode, block_size):
@@ -248,6 +262,41 @@ int pal_tdoa_closure_dev(pal_handle h, const pal_pair_record* d_tables, int B, i
                          pal_closure_frame* d_summary);
 int pal_tdoa_closure(pal_handle h, const pal_pair_record* tables, int B, int M, const int32_t* lengths, int32_t tol, int32_t min_votes,
                      int32_t weight_mode, int32_t* votes, int32_t* mic_closed, double* weights, pal_closure_frame* summary);
+
+/* ---- loop-closure consensus over several candidate peaks per pair (no counterpart in the reference) ------------
+ * The closure check says which pairs are wrong; this call puts them right where the right lag is among the pair's K candidate peaks.
+ * Integer arithmetic on array indices throughout (lag = index - (lengths[b] - 1)): pyaudiolocalization_amd/consensus.py states the rule
+ * index by index and the device equals it byte for byte.
+ *   cand_k[B][P][K]: candidate array indices per pair (P = M(M-1)/2, row-major i<j), highest peak first, -1 = absent; the present
+ *     candidates of a pair form a prefix and candidate 0 is present;  cand_h[B][P][K] (may be NULL): their heights;
+ *   tables[B][P] (may be NULL when table_out is NULL): the records that table_out copies;  lengths[B] (host, read before the call returns);
+ *   stage 0: support of candidate c of pair (i, j) = the third microphones k for which candidates a of pair {i, k} and b of pair {j, k}
+ *     exist with |s(i,k,a) - s(j,k,b) - lag(c)| <= tol (s: the lag, negated when the first index is the larger); the first c with the
+ *     largest support is taken;  then exactly `rounds` Jacobi rounds: a pair keeps its candidate unless another one has strictly more
+ *     closure votes against the lags the other pairs chose in the previous round (then the first c with the most votes);
+ *   sel[B][P]: the chosen candidate;  table_out[B][P]: the records with k_sel the chosen candidate, sel_height its height (when cand_h
+ *     is given) and PAL_BR_CONSENSUS set where sel != 0;  summary[B].  Each of the three outputs may be NULL, not all of them.
+ *     Results do not depend on which other frames share the call.
+ * 3 <= M <= 256, 1 <= K <= PAL_MAX_CANDIDATES, B >= 1, 0 <= tol <= 2^20, 0 <= rounds <= PAL_MAX_CONSENSUS_ROUNDS, 1 <= lengths[b] <= 2^24:
+ * PAL_ERR_INVALID otherwise, and for a present candidate outside 0..2 lengths[b] - 2, an absent candidate 0 or a gap in the prefix: the
+ * host form reports these itself, the _dev form - asynchronous, results complete after pal_synchronize - through pal_synchronize.
+ * What the rule cannot see: among two consistent sources (the source and an image source) the rounds converge on the one that the
+ * majority of first picks lies on; a constant clock offset of one microphone closes every triangle. */
+#define PAL_MAX_CANDIDATES 8
+#define PAL_MAX_CONSENSUS_ROUNDS 8
+#define PAL_BR_CONSENSUS 16   /* branch bit of table_out: the consensus replaced the first peak */
+typedef struct pal_consensus_frame {   /* 16 bytes */
+  int32_t moved;          /* pairs with sel != 0                                                   */
+  int32_t closed_before;  /* closed triangles (within tol) of the table of candidate 0             */
+  int32_t closed_after;   /* ... of the table the call chose                                       */
+  int32_t changed_last;   /* pairs that changed in the last round (rounds = 0: in stage 0)         */
+} pal_consensus_frame;
+int pal_tdoa_consensus_dev(pal_handle h, const pal_pair_record* d_tables, const int32_t* d_cand_k, const double* d_cand_h, int B, int M,
+                           int K, const int32_t* lengths, int32_t tol, int32_t rounds, int32_t* d_sel, pal_pair_record* d_table_out,
+                           pal_consensus_frame* d_summary);
+int pal_tdoa_consensus(pal_handle h, const pal_pair_record* tables, const int32_t* cand_k, const double* cand_h, int B, int M, int K,
+                       const int32_t* lengths, int32_t tol, int32_t rounds, int32_t* sel, pal_pair_record* table_out,
+                       pal_consensus_frame* summary);
 
 /* single-pair signatures: phat_correlation(sig1, sig2) (utils.py:108) -> corr[n1+n2-1] */
 int pal_phat_correlation(pal_handle h, const double* sig1, int n1, const double* sig2, int n2, double* corr);

@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("PAL_LIB_PATH") or os.path.join(_HERE, "libpal_hip.so"
 PAL_MAX_PEAKS = 256
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED, ERR_INTERNAL, ERR_COMM, ERR_MATERIAL = -1, -2, -3, -4, -5, -6, -7
 BR_ALT_THRESHOLD, BR_ARGMAX_NO_PEAKS, BR_WINDOW_RETRY, BR_ARGMAX_WINDOW = 1, 2, 4, 8
+BR_CONSENSUS = 16
+MAX_CANDIDATES = 8
 BOOT_PERMUTATION, BOOT_BLOCK, BOOT_CIRCULAR = 0, 1, 2
 CLOSURE_W_MASK, CLOSURE_W_SOFT = 0, 1
 
@@ -68,6 +70,12 @@ SIGNATURES = {
     "pal_gcc_phat_all_pairs_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(PhatParams), C.c_void_p]),
     "pal_gcc_phat_pairs": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(PhatParams), C.c_void_p]),
     "pal_gcc_phat_pairs_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(PhatParams), C.c_void_p]),
+    "pal_gcc_phat_all_pairs_peaks": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(PhatParams), C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
+    "pal_gcc_phat_all_pairs_peaks_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(PhatParams), C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
+    "pal_gcc_phat_pairs_peaks_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(PhatParams), C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
     "pal_bootstrap_shuffle_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64,
                                             C.c_int32, C.c_void_p]),
     "pal_bootstrap_peaks": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
@@ -86,6 +94,10 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     "pal_tdoa_closure": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "pal_tdoa_consensus_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pal_tdoa_consensus": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "pal_phat_correlation": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "pal_get_time_delays_phat": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(PhatParams), C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

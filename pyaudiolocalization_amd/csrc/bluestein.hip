@@ -447,7 +447,7 @@ int Engine::forward_spectra(Plan& pl, const double* frames, size_t frame_stride,
 // explicit pair list over R equal-length rows, everything in HBM: one-vs-many bootstrap batches, sparse pair sets, and
 // the contiguous pair blocks a rank owns when ONE large frame is split over the GPUs (spectra recomputed locally)
 int Engine::pairs_dev(const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P, const pal_phat_params& prm,
-                      pal_pair_record* d_table) {
+                      pal_pair_record* d_table, const CandOut* cands) {
   if (R < 1 || L < 1 || P < 1) return fail(PAL_ERR_INVALID, "need R >= 1, L >= 1, P >= 1");
   if (L > (1 << 20)) return fail(PAL_ERR_UNSUPPORTED, "frame length %d exceeds 2^20", L);
   Plan* pl = nullptr;
@@ -463,12 +463,23 @@ int Engine::pairs_dev(const double* d_rows, int R, int L, const int32_t* d_pairs
   k_pairs_to_quads<<<dim3(unsigned((ntr + 255) / 256)), dim3(256), 0, stream>>>(d_pairs, P, R, dq, status);
   PAL_HIP(hipGetLastError());
   PAL_TRY(forward_spectra(*pl, d_rows, size_t(L), R, L, sp, nonzero));
-  return pair_correlations(*pl, sp, R, dq, P, L, prm, d_table, nullptr, nullptr, nonzero);
+  return pair_correlations(*pl, sp, R, dq, P, L, prm, d_table, nullptr, nullptr, nonzero, false, cands);
+}
+
+// the first K of a launch group's PAL_MAX_PEAKS-wide selection rows -> the caller's K columns (indices -1, heights +0.0 past n_sel)
+__global__ __launch_bounds__(256) void k_compact_cands(const int32_t* __restrict__ ksel, const double* __restrict__ hsel, int rows, int K,
+                                                       int32_t* __restrict__ cand_k, double* __restrict__ cand_h) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= rows * K) return;
+  const int r = t / K, c = t % K;
+  const int32_t k = ksel[size_t(r) * PAL_MAX_PEAKS + c];
+  cand_k[size_t(r) * K + c] = k;
+  if (cand_h) cand_h[size_t(r) * K + c] = k >= 0 ? hsel[size_t(r) * PAL_MAX_PEAKS + c] : 0.0;
 }
 
 int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4* quads, int64_t npairs, int n2,
                               const pal_phat_params& prm, pal_pair_record* table, int32_t* ksel_multi,
-                              double* corr_out, const int* nonzero, bool stored_only) {
+                              double* corr_out, const int* nonzero, bool stored_only, const CandOut* cands) {
   const Conv& c = pl.inv;
   const int n = pl.n;
   const bool pfa = pl.pfa.on();
@@ -494,11 +505,21 @@ int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4
   // who transforms a launch group and who computes its rows' statistics: one decision per call (pair_route.h)
   const Pfa& f = pl.pfa;
   const PairRoute route = pair_route(RouteIn{n, pl.nout, pfa, f.n1, f.n2, f.nch, f.lm, f.r89, table != nullptr, corr_out != nullptr,
-                                             ksel_multi != nullptr, npairs, stored_only, prm.num_peaks, prm.threshold_method, prm.threshold_multiplier,
+                                             ksel_multi != nullptr || cands != nullptr, npairs, stored_only, prm.num_peaks, prm.threshold_method, prm.threshold_multiplier,
                                              fin_cols, fuse_peaks, lean_store, rows_lean, rows_lean_min});
   // the finishing passes and k_rows_lean write one flag per pair: 1 = resolved at the end of this call from stored rows
   int* need = nullptr;
   if (route.flags_pairs()) PAL_TRY(scratch(kWsFlags, (size_t(2 * npairs) + 64) * sizeof(int), &need));     // [flags | list | count]
+  // candidates: the PAL_MAX_PEAKS-wide selection rows of a launch group stay in scratch per stream slot (reuse ordered by the slot's
+  // stream) and k_compact_cands, on that stream, writes their first K columns at the group's place in the caller's buffers
+  const size_t cand_rows = size_t(2 * chunk) * PAL_MAX_PEAKS;
+  int32_t* cand_kbuf = nullptr;
+  double* cand_hbuf = nullptr;
+  if (cands) {
+    if (!table || !cands->k || prm.num_peaks > PAL_MAX_CANDIDATES) return fail(PAL_ERR_INVALID, "candidates need a table, a buffer and num_peaks <= %d", PAL_MAX_CANDIDATES);
+    PAL_TRY(scratch(kWsCandK, size_t(nslot) * cand_rows * sizeof(int32_t), &cand_kbuf));
+    PAL_TRY(scratch(kWsCandH, size_t(nslot) * cand_rows * sizeof(double), &cand_hbuf));
+  }
   if (nslot == 3) {   // the other streams start after everything already queued on `stream` (spectra, pair table)
     PAL_HIP(hipEventRecord(ev_fork, stream));
     PAL_HIP(hipStreamWaitEvent(stream2, ev_fork, 0));
@@ -517,14 +538,15 @@ int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4
     const bool via_scratch = !corr_out || rows < 2 * G;
     double* crow = via_scratch ? cbuf + size_t(slot) * buf_doubles : corr_out + size_t(p0) * stride;
     const int* zrows = zero_rows ? zero_rows + p0 : nullptr;
-    int32_t* ksel = ksel_multi ? ksel_multi + p0 * PAL_MAX_PEAKS : nullptr;
+    int32_t* ksel = cands ? cand_kbuf + size_t(slot) * cand_rows : (ksel_multi ? ksel_multi + p0 * PAL_MAX_PEAKS : nullptr);
+    double* hsel = cands ? cand_hbuf + size_t(slot) * cand_rows : nullptr;
     switch (route.transform) {   // (forward_spectra wrote the (k mod N1, k mod N2) layout when the plan has the split)
       case RouteTransform::kFinish:      // nobody reads the correlation rows: the column pass finishes them without storing them (pfa_cols_fin.h)
         PAL_TRY(pfa_pair_group_fin(pl, spectra, quads + t0, G, rows, Wg, zrows, prm, n2, table + p0, need + p0, slot)); break;
       case RouteTransform::kLeanStore:   // stored rows + per-wavefront statistics (pfa_fin_lean.h with FinArgs.corr)
         PAL_TRY(pfa_pair_group_fin(pl, spectra, quads + t0, G, rows, Wg, zrows, prm, n2, table + p0, need + p0, slot, crow, stride)); break;
       case RouteTransform::kFused:
-        PAL_TRY(pfa_pair_group_fused(pl, spectra, quads + t0, G, rows, Wg, crow, stride, zrows, prm, n2, table + p0, ksel, slot)); break;
+        PAL_TRY(pfa_pair_group_fused(pl, spectra, quads + t0, G, rows, Wg, crow, stride, zrows, prm, n2, table + p0, ksel, slot, hsel)); break;
       case RouteTransform::kPfa:
         PAL_TRY(pfa_pair_group(pl, spectra, quads + t0, G, Wg, crow, stride, zrows, on)); break;
       case RouteTransform::kFourStep: {
@@ -541,7 +563,12 @@ int Engine::pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4
                              hipMemcpyDeviceToDevice, on));
     // rows of the plain routes: their statistics in one launch over the stored rows, or in three
     if (route.stats == RouteStats::kRowsLean) PAL_TRY(rows_lean_group(pl, crow, stride, G, rows, prm, n2, table + p0, need + p0, slot));
-    else if (route.stats == RouteStats::kThreeLaunches) PAL_TRY(peaks(crow, stride, rows, n, n2, prm, table + p0, ksel, slot));
+    else if (route.stats == RouteStats::kThreeLaunches) PAL_TRY(peaks(crow, stride, rows, n, n2, prm, table + p0, ksel, slot, hsel));
+    if (cands) {
+      const int K = prm.num_peaks;
+      k_compact_cands<<<dim3(unsigned((rows * K + 255) / 256)), dim3(256), 0, on>>>(ksel, hsel, rows, K, cands->k + p0 * K, cands->h ? cands->h + p0 * K : nullptr);
+      PAL_HIP(hipGetLastError());
+    }
     return PAL_OK;
   };
   int64_t group = 0;

@@ -90,11 +90,20 @@ enum Ws : int {
   kWsResample = 24,    // resample.hip: the interleaved (win, delta) filter table of the latest ratio
   kWsClosure = 25,     // the closure check (closure.hip): frame lengths, dense lag matrices, votes when the caller takes none
   kWsFinStrip0 = 26, kWsFinStrip1 = 27, kWsFinStrip2 = 28,   // its SNR strips (pair_route.h fin_strip) per stream slot, see fin_strip_slot
-  kWsCount = 29
+  kWsConsensus = 29,   // the consensus (consensus.hip): frame lengths, candidate cubes, chosen-lag matrices, three selections, two vote tables
+  kWsCandK = 30, kWsCandH = 31,   // the selected peaks of a launch group per stream slot (PAL_MAX_PEAKS indices / heights per row), compacted into a CandOut
+  kWsCount = 32
 };
 constexpr Ws peak_scratch_slot(int slot) { return slot == 0 ? kWsPeaks0 : (slot == 1 ? kWsPeaks1 : kWsPeaks2); }
 constexpr Ws fin_scratch_slot(int slot) { return Ws(kWsFin0 + slot); }
 constexpr Ws fin_strip_slot(int slot) { return Ws(kWsFinStrip0 + slot); }
+
+// K = num_peaks candidate peaks per pair of a batched call (pal_gcc_phat_*_peaks*): k[npairs][K] array indices, -1 past n_sel;
+// h[npairs][K] heights, +0.0 past n_sel, or nullptr
+struct CandOut {
+  int32_t* k;
+  double* h;
+};
 
 struct Engine {
   int device = 0;
@@ -196,9 +205,10 @@ struct Engine {
   int forward_spectra(Plan& pl, const double* frames, size_t frame_stride, int rows, int len, cd* spectra, int* nonzero = nullptr);
   int pair_correlations(Plan& pl, const cd* spectra, int nspec, const int4* quads, int64_t npairs, int n2,
                         const pal_phat_params& prm, pal_pair_record* table, int32_t* ksel_multi, double* corr_out,
-                        const int* nonzero = nullptr, bool stored_only = false);   // stored_only: the repair pass of flagged pairs (pair_route.h)
+                        const int* nonzero = nullptr, bool stored_only = false,    // stored_only: the repair pass of flagged pairs (pair_route.h)
+                        const CandOut* cands = nullptr);                           // cands: K candidate peaks per pair into the caller's buffers
   int pairs_dev(const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P, const pal_phat_params& prm,
-                pal_pair_record* d_table);
+                pal_pair_record* d_table, const CandOut* cands = nullptr);
   // bootstrap.hip: counter-based shuffles (pal_bootstrap_shuffle_dev) and the shuffled pairs through the pair pipeline, round by round
   int bootstrap_shuffle_dev(const double* d_row, int L, int32_t i, int32_t j, int32_t mode, int32_t block_size, uint64_t seed, int64_t s0,
                             int32_t S, double* d_out);
@@ -219,6 +229,11 @@ struct Engine {
   int tdoa_closure_dev(const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, int32_t tol, int32_t min_votes, int32_t weight_mode,
                        int32_t* d_votes, int32_t* d_mic_closed, double* d_weights, pal_closure_frame* d_summary);
   int closure_check(int B, int M, const int32_t* lengths, int32_t tol, int32_t min_votes, int32_t weight_mode);
+  // consensus.hip: loop-closure consensus over K candidates per pair (every pointer but `lengths` in HBM, each output or nullptr); asynchronous
+  int tdoa_consensus_dev(const pal_pair_record* d_tables, const int32_t* d_cand_k, const double* d_cand_h, int B, int M, int K,
+                         const int32_t* lengths, int32_t tol, int32_t rounds, int32_t* d_sel, pal_pair_record* d_table_out,
+                         pal_consensus_frame* d_summary);
+  int consensus_check(int B, int M, int K, const int32_t* lengths, int32_t tol, int32_t rounds);
   int32_t* solve_idx = nullptr;    // device table pair -> i | j << 16 of the last microphone count
   int solve_idx_M = 0;
   // resample.hip: the right wing of the interpolation filter as pal_resample_set_filter received it, and the ratio whose scaled
@@ -228,12 +243,12 @@ struct Engine {
   int rs_num_table = 0;
   double rs_ratio = 0;
   int peaks(const double* corr, size_t stride, int rows, int n, int n2, const pal_phat_params& prm,
-            pal_pair_record* table, int32_t* ksel_multi, int slot);
+            pal_pair_record* table, int32_t* ksel_multi, int slot, double* hsel_multi = nullptr);   // hsel_multi: heights beside ksel_multi's indices
   // the same in pieces, for the column pass that produces the streaming statistics itself (pfa_cols_stats.h):
   // arguments + scratch (segments = `blocks` column blocks of a grid with rows of grid_n2, each with its own pivots),
   // [the caller's fused column launch], the finish launch
   int peaks_setup(const double* corr, size_t stride, int rows, int n, int n2, const pal_phat_params& prm, int blocks, int grid_n2, int slot, PeakArgs& a);
-  int peaks_finish(PeakArgs& a, int rows, pal_pair_record* table, int32_t* ksel_multi, int slot);
+  int peaks_finish(PeakArgs& a, int rows, pal_pair_record* table, int32_t* ksel_multi, int slot, double* hsel_multi = nullptr);
   int pfa_rows(const Plan& pl, const cd* permuted, const int4* quads, int G, cd* Y, hipStream_t on);
   int fin_setup(const Plan& pl, int rows, int nblk, int grid_rows, const pal_phat_params& prm, int n2, pal_pair_record* table,
                 int* need, int slot, PeakArgs& a, struct FinArgs& fa, unsigned& nwg, int G);
@@ -243,7 +258,8 @@ struct Engine {
                          const pal_phat_params& prm, int n2, pal_pair_record* table, int* need, int slot,
                          double* corr = nullptr, size_t stride = 0);
   int pfa_pair_group_fused(const Plan& pl, const cd* permuted, const int4* quads, int G, int rows, cd* Y, double* corr, size_t stride,
-                           const int* zero_rows, const pal_phat_params& prm, int n2, pal_pair_record* table, int32_t* ksel_multi, int slot);
+                           const int* zero_rows, const pal_phat_params& prm, int n2, pal_pair_record* table, int32_t* ksel_multi, int slot,
+                           double* hsel_multi = nullptr);
   bool pfa_forward_applies(const Plan& pl, int len) const;
   int pfa_forward_spectra(Plan& pl, const double* frames, size_t frame_stride, int rows, int len, cd* spectra, const int* flags);
   bool pfa_forward = true;    // PAL_PFA_FWD=0: forward spectra on the four-step route even where the prime-factor cut applies

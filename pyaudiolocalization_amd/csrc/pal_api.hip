@@ -122,6 +122,8 @@ static int check_status(Engine* e) {
     hipMemset(dev + kStInput, 0, sizeof(int));
     if (st[kStInput] & kStInputBadRow) return e->fail(PAL_ERR_INVALID, "pair list references a row outside the frame batch");
     if (st[kStInput] & kStInputBadLag) return e->fail(PAL_ERR_INVALID, "a record of the TDOA table has k_sel outside 0..2 length - 2: the closure results of this call are not valid");
+    if (st[kStInput] & kStInputBadCandidate)
+      return e->fail(PAL_ERR_INVALID, "a candidate outside 0..2 length - 2, an absent candidate 0 or a gap in a pair's candidates: the consensus results of this call are not valid");
     return e->fail(PAL_ERR_INVALID, "non-finite sample (NaN or infinity) in a frame: the pair packed with that microphone's "
                                     "pairs would be affected too, the table of this call is not valid");
   }
@@ -183,7 +185,7 @@ __global__ __launch_bounds__(256) void k_scatter_records(const pal_pair_record* 
 }
 
 static int all_pairs_dev(Engine* e, const double* d_frames, int B, int M, int L, const pal_phat_params* prm,
-                         pal_pair_record* d_table, double* d_corr) {
+                         pal_pair_record* d_table, double* d_corr, const CandOut* cands = nullptr) {
   PAL_TRY(validate(e, prm));
   if (B < 1 || M < 2 || L < 1) return e->fail(PAL_ERR_INVALID, "need B >= 1, M >= 2, L >= 1 (got %d, %d, %d)", B, M, L);
   if (int64_t(B) * M > INT32_MAX / 2) return e->fail(PAL_ERR_UNSUPPORTED, "too many rows");
@@ -198,7 +200,7 @@ static int all_pairs_dev(Engine* e, const double* d_frames, int B, int M, int L,
   PAL_TRY(e->forward_spectra(*pl, d_frames, size_t(L), rows, L, spectra, nonzero));
   // the pair table depends on (B, M) only: keep it on the device between calls of the same shape
   const size_t nquads = size_t((int64_t(B) * M * (M - 1) / 2 + 1) / 2);
-  if (e->pair_block > 1 && M >= 96 && !d_corr && int64_t(B) * M * (M - 1) / 2 < INT32_MAX) {
+  if (e->pair_block > 1 && M >= 96 && !d_corr && !cands && int64_t(B) * M * (M - 1) / 2 < INT32_MAX) {
     const int64_t np = int64_t(B) * M * (M - 1) / 2;
     if (e->blk_B != B || e->blk_M != M || !e->quads_blk) {
       std::vector<int4> quads;
@@ -233,7 +235,7 @@ static int all_pairs_dev(Engine* e, const double* d_frames, int B, int M, int L,
   }
   void* qp = e->quads;
   const int64_t np = int64_t(B) * M * (M - 1) / 2;
-  return e->pair_correlations(*pl, spectra, rows, static_cast<const int4*>(qp), np, L, *prm, d_table, nullptr, d_corr, nonzero);
+  return e->pair_correlations(*pl, spectra, rows, static_cast<const int4*>(qp), np, L, *prm, d_table, nullptr, d_corr, nonzero, false, cands);
 }
 
 // explicit pair list over R equal-length rows (host buffers): upload, then the device-resident form
@@ -475,6 +477,54 @@ int pal_gcc_phat_pairs_dev(pal_handle h, const double* d_rows, int R, int L, con
   return e->pairs_dev(d_rows, R, L, d_pairs, P, *prm, d_table);
 }
 
+// ---- K candidate peaks per pair from the batched calls (K = prm->num_peaks in 1 .. PAL_MAX_CANDIDATES) ----
+static int validate_peaks(Engine* e, const pal_phat_params* p) {
+  PAL_TRY(validate(e, p));
+  if (p->num_peaks > PAL_MAX_CANDIDATES) return e->fail(PAL_ERR_INVALID, "num_peaks %d outside 1..%d", p->num_peaks, PAL_MAX_CANDIDATES);
+  return PAL_OK;
+}
+
+int pal_gcc_phat_all_pairs_peaks_dev(pal_handle h, const double* d_frames, int B, int M, int L, const pal_phat_params* prm,
+                                     pal_pair_record* d_table, int32_t* d_cand_k, double* d_cand_h) {
+  ENGINE(h);
+  PAL_TRY(validate_peaks(e, prm));
+  if (!d_frames || !d_table || !d_cand_k) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  const CandOut cands{d_cand_k, d_cand_h};
+  return all_pairs_dev(e, d_frames, B, M, L, prm, d_table, nullptr, &cands);
+}
+
+int pal_gcc_phat_all_pairs_peaks(pal_handle h, const double* frames, int B, int M, int L, const pal_phat_params* prm,
+                                 pal_pair_record* table, int32_t* cand_k, double* cand_h) {
+  ENGINE(h);
+  PAL_TRY(validate_peaks(e, prm));
+  if (!frames || !table || !cand_k) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  if (B < 1 || M < 2 || L < 1) return e->fail(PAL_ERR_INVALID, "need B >= 1, M >= 2, L >= 1 (got %d, %d, %d)", B, M, L);
+  const size_t fbytes = size_t(B) * M * L * sizeof(double);
+  const size_t np = size_t(int64_t(B) * M * (M - 1) / 2), nc = np * size_t(prm->num_peaks);
+  const size_t o_h = (nc * sizeof(int32_t) + 255) & ~size_t(255);
+  void *df = nullptr, *dt = nullptr;
+  char* dc = nullptr;
+  PAL_TRY(e->scratch(kWsStageIn, fbytes, &df));
+  PAL_TRY(e->scratch(kWsStageTable, np * sizeof(pal_pair_record), &dt));
+  PAL_TRY(e->scratch(kWsStageOut, o_h + nc * sizeof(double), &dc));   // [cand_k | cand_h]
+  PAL_TRY(e->check(hipMemcpyAsync(df, frames, fbytes, hipMemcpyHostToDevice, e->stream), "frames upload"));
+  const CandOut cands{reinterpret_cast<int32_t*>(dc), cand_h ? reinterpret_cast<double*>(dc + o_h) : nullptr};
+  PAL_TRY(all_pairs_dev(e, static_cast<const double*>(df), B, M, L, prm, static_cast<pal_pair_record*>(dt), nullptr, &cands));
+  PAL_TRY(e->check(hipMemcpyAsync(table, dt, np * sizeof(pal_pair_record), hipMemcpyDeviceToHost, e->stream), "table download"));
+  PAL_TRY(e->check(hipMemcpyAsync(cand_k, cands.k, nc * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "candidates download"));
+  if (cand_h) PAL_TRY(e->check(hipMemcpyAsync(cand_h, cands.h, nc * sizeof(double), hipMemcpyDeviceToHost, e->stream), "heights download"));
+  return pal_synchronize(h);
+}
+
+int pal_gcc_phat_pairs_peaks_dev(pal_handle h, const double* d_rows, int R, int L, const int32_t* d_pairs, int64_t P,
+                                 const pal_phat_params* prm, pal_pair_record* d_table, int32_t* d_cand_k, double* d_cand_h) {
+  ENGINE(h);
+  PAL_TRY(validate_peaks(e, prm));
+  if (!d_rows || !d_pairs || !d_table || !d_cand_k) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  const CandOut cands{d_cand_k, d_cand_h};
+  return e->pairs_dev(d_rows, R, L, d_pairs, P, *prm, d_table, &cands);
+}
+
 int pal_bootstrap_shuffle_dev(pal_handle h, const double* d_row, int L, int32_t i, int32_t j, int32_t mode, int32_t block_size,
                               uint64_t seed, int64_t s0, int32_t S, double* d_out) {
   ENGINE(h);
@@ -599,6 +649,65 @@ int pal_tdoa_closure(pal_handle h, const pal_pair_record* tables, int B, int M, 
   if (mic_closed) PAL_TRY(e->check(hipMemcpyAsync(mic_closed, dm, size_t(B) * M * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "mic_closed download"));
   if (weights) PAL_TRY(e->check(hipMemcpyAsync(weights, dw, np * sizeof(double), hipMemcpyDeviceToHost, e->stream), "weights download"));
   if (summary) PAL_TRY(e->check(hipMemcpyAsync(summary, ds, size_t(B) * sizeof(pal_closure_frame), hipMemcpyDeviceToHost, e->stream), "summary download"));
+  return pal_synchronize(h);
+}
+
+int pal_tdoa_consensus_dev(pal_handle h, const pal_pair_record* d_tables, const int32_t* d_cand_k, const double* d_cand_h, int B, int M,
+                           int K, const int32_t* lengths, int32_t tol, int32_t rounds, int32_t* d_sel, pal_pair_record* d_table_out,
+                           pal_consensus_frame* d_summary) {
+  ENGINE(h);
+  return e->tdoa_consensus_dev(d_tables, d_cand_k, d_cand_h, B, M, K, lengths, tol, rounds, d_sel, d_table_out, d_summary);
+}
+
+int pal_tdoa_consensus(pal_handle h, const pal_pair_record* tables, const int32_t* cand_k, const double* cand_h, int B, int M, int K,
+                       const int32_t* lengths, int32_t tol, int32_t rounds, int32_t* sel, pal_pair_record* table_out,
+                       pal_consensus_frame* summary) {
+  ENGINE(h);
+  PAL_TRY(e->consensus_check(B, M, K, lengths, tol, rounds));
+  if (!cand_k) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  if (!sel && !table_out && !summary) return e->fail(PAL_ERR_INVALID, "no output requested");
+  if (table_out && !tables) return e->fail(PAL_ERR_INVALID, "table_out needs the input tables");
+  const size_t P = size_t(M) * size_t(M - 1) / 2, np = size_t(B) * P;
+  for (size_t r = 0; r < np; ++r) {
+    const int64_t len = lengths[r / P];
+    bool ended = false;
+    for (int c = 0; c < K; ++c) {
+      const int64_t k = cand_k[r * K + c];
+      if (k == -1) {
+        if (c == 0) return e->fail(PAL_ERR_INVALID, "frame %d, pair %d: candidate 0 is absent", int(r / P), int(r % P));
+        ended = true;
+      } else if (ended) {
+        return e->fail(PAL_ERR_INVALID, "frame %d, pair %d: candidate %d follows an absent one", int(r / P), int(r % P), c);
+      } else if (k < 0 || k > 2 * len - 2) {
+        return e->fail(PAL_ERR_INVALID, "frame %d, pair %d: candidate %d is %d, outside 0..%d", int(r / P), int(r % P), c, int(k), int(2 * len - 2));
+      }
+    }
+  }
+  // staged inputs [cand_k | cand_h] and outputs [sel | table_out | summary], one block each
+  auto align = [](size_t v) { return (v + 255) & ~size_t(255); };
+  const size_t nc = np * size_t(K);
+  const size_t o_h = align(nc * sizeof(int32_t)), in_total = o_h + align(cand_h ? nc * sizeof(double) : 0);
+  const size_t o_tab = align(sel ? np * sizeof(int32_t) : 0);
+  const size_t o_sum = o_tab + align(table_out ? np * sizeof(pal_pair_record) : 0);
+  const size_t total = o_sum + align(summary ? size_t(B) * sizeof(pal_consensus_frame) : 0);
+  void* dt = nullptr;
+  char *in = nullptr, *out = nullptr;
+  if (tables) {
+    PAL_TRY(e->scratch(kWsStageTable, np * sizeof(pal_pair_record), &dt));
+    PAL_TRY(e->check(hipMemcpyAsync(dt, tables, np * sizeof(pal_pair_record), hipMemcpyHostToDevice, e->stream), "tables upload"));
+  }
+  PAL_TRY(e->scratch(kWsStageIn, in_total, &in));
+  PAL_TRY(e->scratch(kWsStageOut, total, &out));
+  PAL_TRY(e->check(hipMemcpyAsync(in, cand_k, nc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream), "candidates upload"));
+  if (cand_h) PAL_TRY(e->check(hipMemcpyAsync(in + o_h, cand_h, nc * sizeof(double), hipMemcpyHostToDevice, e->stream), "heights upload"));
+  int32_t* ds = sel ? reinterpret_cast<int32_t*>(out) : nullptr;
+  pal_pair_record* dto = table_out ? reinterpret_cast<pal_pair_record*>(out + o_tab) : nullptr;
+  pal_consensus_frame* dsum = summary ? reinterpret_cast<pal_consensus_frame*>(out + o_sum) : nullptr;
+  PAL_TRY(e->tdoa_consensus_dev(static_cast<const pal_pair_record*>(dt), reinterpret_cast<const int32_t*>(in),
+                                cand_h ? reinterpret_cast<const double*>(in + o_h) : nullptr, B, M, K, lengths, tol, rounds, ds, dto, dsum));
+  if (sel) PAL_TRY(e->check(hipMemcpyAsync(sel, ds, np * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "sel download"));
+  if (table_out) PAL_TRY(e->check(hipMemcpyAsync(table_out, dto, np * sizeof(pal_pair_record), hipMemcpyDeviceToHost, e->stream), "table download"));
+  if (summary) PAL_TRY(e->check(hipMemcpyAsync(summary, dsum, size_t(B) * sizeof(pal_consensus_frame), hipMemcpyDeviceToHost, e->stream), "summary download"));
   return pal_synchronize(h);
 }
 

@@ -1240,7 +1240,7 @@ __device__ __forceinline__ bool fallback_chain(const SelArgs sa, const double* c
 }
 
 template <bool LOCAL>   // LOCAL: the segments are column blocks of the fused column pass (histogram windows, no pivots)
-__device__ __forceinline__ void finish_row(const PeakArgs& a, pal_pair_record* table, int32_t* ksel_multi, int* status, const int row) {
+__device__ __forceinline__ void finish_row(const PeakArgs& a, pal_pair_record* table, int32_t* ksel_multi, double* hsel_multi, int* status, const int row) {
   __shared__ Shared s;
   __shared__ Partial sparts[kMaxStaged];
   const int tid = threadIdx.x;
@@ -1318,13 +1318,15 @@ __device__ __forceinline__ void finish_row(const PeakArgs& a, pal_pair_record* t
     table[row] = rec;
     if (ksel_multi)
       for (int k = 0; k < PAL_MAX_PEAKS; ++k) ksel_multi[size_t(row) * PAL_MAX_PEAKS + k] = k < ch.count ? s.sel_pos[k] : -1;
+    if (hsel_multi)                                            // heights of the selected peaks only: the reader goes by ksel_multi
+      for (int k = 0; k < ch.count; ++k) hsel_multi[size_t(row) * PAL_MAX_PEAKS + k] = s.sel_h[k];
     if (ch.overflow) atomicOr(status + kStOverflow, 1);
   }
 }
 
 template <bool LOCAL>
-__global__ __launch_bounds__(kT, 4) void k_peak_finish(PeakArgs a, pal_pair_record* table, int32_t* ksel_multi, int* status) {   // (4 waves per SIMD = two workgroups per CU: the launch is latency-bound)
-  finish_row<LOCAL>(a, table, ksel_multi, status, blockIdx.x);
+__global__ __launch_bounds__(kT, 4) void k_peak_finish(PeakArgs a, pal_pair_record* table, int32_t* ksel_multi, double* hsel_multi, int* status) {   // (4 waves per SIMD = two workgroups per CU: the launch is latency-bound)
+  finish_row<LOCAL>(a, table, ksel_multi, hsel_multi, status, blockIdx.x);
 }
 
 }  // namespace
@@ -1381,22 +1383,22 @@ int Engine::peaks_setup(const double* corr, size_t stride, int rows, int n, int 
   return PAL_OK;
 }
 
-int Engine::peaks_finish(PeakArgs& a, int rows, pal_pair_record* table, int32_t* ksel_multi, int slot) {
+int Engine::peaks_finish(PeakArgs& a, int rows, pal_pair_record* table, int32_t* ksel_multi, int slot, double* hsel_multi) {
   const bool metrics_only = a.method < 0;
   const hipStream_t on = stream_of(slot);
   int* status = nullptr;
   PAL_TRY(status_words(&status));
   {
     ProfScope ps(this, metrics_only ? "k_peak_finish(metrics)" : "k_peak_finish", on);
-    if (a.tiles_per_seg == 0) k_peak_finish<true><<<dim3(rows), dim3(kT), 0, on>>>(a, table, ksel_multi, status);
-    else k_peak_finish<false><<<dim3(rows), dim3(kT), 0, on>>>(a, table, ksel_multi, status);
+    if (a.tiles_per_seg == 0) k_peak_finish<true><<<dim3(rows), dim3(kT), 0, on>>>(a, table, ksel_multi, hsel_multi, status);
+    else k_peak_finish<false><<<dim3(rows), dim3(kT), 0, on>>>(a, table, ksel_multi, hsel_multi, status);
     PAL_HIP(hipGetLastError());
   }
   return PAL_OK;
 }
 
 int Engine::peaks(const double* corr, size_t stride, int rows, int n, int n2, const pal_phat_params& prm,
-                  pal_pair_record* table, int32_t* ksel_multi, int slot) {
+                  pal_pair_record* table, int32_t* ksel_multi, int slot, double* hsel_multi) {
   if (rows <= 0) return PAL_OK;
   const hipStream_t on = stream_of(slot);
   PeakArgs a;
@@ -1411,7 +1413,7 @@ int Engine::peaks(const double* corr, size_t stride, int rows, int n, int n2, co
     k_peak_stream<<<dim3(unsigned(rows) * unsigned(a.splits)), dim3(kTS), 0, on>>>(a);
     PAL_HIP(hipGetLastError());
   }
-  return peaks_finish(a, rows, table, ksel_multi, slot);
+  return peaks_finish(a, rows, table, ksel_multi, slot, hsel_multi);
 }
 
 }  // namespace pal

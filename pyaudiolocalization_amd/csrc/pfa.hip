@@ -208,7 +208,7 @@ int Engine::pfa_forward_spectra(Plan& pl, const double* frames, size_t frame_str
 // read of its correlation rows (pfa_cols_stats.h)
 int Engine::pfa_pair_group_fused(const Plan& pl, const cd* permuted, const int4* quads, int G, int rows, cd* Y, double* corr, size_t stride,
                                  const int* zero_rows, const pal_phat_params& prm, int n2, pal_pair_record* table, int32_t* ksel_multi,
-                                 int slot) {
+                                 int slot, double* hsel_multi) {
   const Pfa& f = pl.pfa;
   const hipStream_t on = stream_of(slot);
   // short column DFTs (one chunk: N1 <= 23): the four wavefronts of a workgroup take four neighbouring strips
@@ -235,7 +235,7 @@ int Engine::pfa_pair_group_fused(const Plan& pl, const cd* permuted, const int4*
 #undef PAL_COLS_STATS
     PAL_HIP(hipGetLastError());
   }
-  return peaks_finish(a, rows, table, ksel_multi, slot);
+  return peaks_finish(a, rows, table, ksel_multi, slot, hsel_multi);
 }
 
 // ---- the column pass that finishes the rows itself (pfa_cols_fin.h, pfa_fin_lean.h): no correlation rows in HBM, no finish launch ----

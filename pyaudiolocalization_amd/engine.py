@@ -13,7 +13,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _ffi, bootstrap, closure, solve
+from . import _ffi, bootstrap, closure, consensus, solve
 from ._ffi import RECORD, PalError, PhatParams, SolveParams, f64, ptr
 
 
@@ -157,6 +157,46 @@ class Engine:
         self._check(self._lib.pal_gcc_phat_all_pairs_dev(self._h, C.c_void_p(d_frames), b, m, length, C.byref(prm),
                                                          C.c_void_p(d_table)))
 
+    def gcc_phat_all_pairs_peaks(self, frames, fs, num_peaks=4, threshold_method="median", threshold_multiplier=1.0, max_expected_delay=None):
+        """frames[B][M][L] (or [M][L]) -> (table[B][P], cand_k[B][P][num_peaks] int32, cand_h[B][P][num_peaks]): the ordinary table (the
+        records of the first peak) and the ``num_peaks`` (1 .. 8) selected peaks per pair, highest first: array indices (-1 past n_sel)
+        and heights (+0.0 past n_sel) - the candidates of ``tdoa_consensus``."""
+        x = f64(frames)
+        squeeze = x.ndim == 2
+        if squeeze:
+            x = x[None]
+        if x.ndim != 3:
+            raise ValueError("frames must be [M][L] or [B][M][L]")
+        k = int(num_peaks)
+        if not 1 <= k <= _ffi.MAX_CANDIDATES:
+            raise ValueError(f"num_peaks {k} outside 1..{_ffi.MAX_CANDIDATES}")
+        b, m, length = x.shape
+        npairs = m * (m - 1) // 2
+        table = np.zeros((b, npairs), dtype=RECORD)
+        cand_k = np.zeros((b, npairs, k), dtype=np.int32)
+        cand_h = np.zeros((b, npairs, k), dtype=np.float64)
+        prm = make_params(fs, k, threshold_method, threshold_multiplier, max_expected_delay)
+        self._check(self._lib.pal_gcc_phat_all_pairs_peaks(self._h, x.ctypes.data, b, m, length, C.byref(prm), table.ctypes.data,
+                                                           cand_k.ctypes.data, cand_h.ctypes.data))
+        return (table[0], cand_k[0], cand_h[0]) if squeeze else (table, cand_k, cand_h)
+
+    def gcc_phat_all_pairs_peaks_dev(self, d_frames: int, b: int, m: int, length: int, prm: PhatParams, d_table: int, d_cand_k: int,
+                                     d_cand_h: int = 0) -> None:
+        """Asynchronous: frames, table, cand_k[b][P][prm.num_peaks] (int32) and cand_h (float64; 0 = not wanted) stay in HBM."""
+        if not 1 <= int(prm.num_peaks) <= _ffi.MAX_CANDIDATES:
+            raise ValueError(f"num_peaks {int(prm.num_peaks)} outside 1..{_ffi.MAX_CANDIDATES}")
+        self._check(self._lib.pal_gcc_phat_all_pairs_peaks_dev(self._h, C.c_void_p(d_frames), b, m, length, C.byref(prm), C.c_void_p(d_table),
+                                                               C.c_void_p(d_cand_k), C.c_void_p(d_cand_h) if d_cand_h else None))
+
+    def gcc_phat_pairs_peaks_dev(self, d_rows: int, r: int, length: int, d_pairs: int, p: int, prm: PhatParams, d_table: int, d_cand_k: int,
+                                 d_cand_h: int = 0) -> None:
+        """Asynchronous: as gcc_phat_pairs_dev, with cand_k[P][prm.num_peaks] and cand_h (0 = not wanted) in HBM."""
+        if not 1 <= int(prm.num_peaks) <= _ffi.MAX_CANDIDATES:
+            raise ValueError(f"num_peaks {int(prm.num_peaks)} outside 1..{_ffi.MAX_CANDIDATES}")
+        self._check(self._lib.pal_gcc_phat_pairs_peaks_dev(self._h, C.c_void_p(d_rows), int(r), int(length), C.c_void_p(d_pairs), int(p),
+                                                           C.byref(prm), C.c_void_p(d_table), C.c_void_p(d_cand_k),
+                                                           C.c_void_p(d_cand_h) if d_cand_h else None))
+
     def gcc_phat_pairs(self, rows, pairs, fs, threshold_method="median", threshold_multiplier=1.0,
                        max_expected_delay=None) -> np.ndarray:
         """rows[R][L] and an explicit pair list pairs[P][2] (row indices) -> table[P]."""
@@ -265,6 +305,46 @@ class Engine:
         finally:
             self.free(d_w)
         return w
+
+    # ---- loop-closure consensus over several candidates per pair (specification: consensus.py) -----
+    def tdoa_consensus(self, cand_k, lengths, m: int, tol: int = 1, rounds: int = 2, tables=None, cand_h=None, outputs=None):
+        """cand_k[B][P][K] (or [P][K]) int32 array indices (-1 = absent), lengths[B] (or one length), m microphones -> (sel[B][P] int32,
+        table_out[B][P] of _ffi.RECORD, summary[B] of consensus.SUMMARY): per pair the candidate the other pairs' candidates agree with
+        (stage 0, then ``rounds`` Jacobi rounds at ``tol`` samples - see consensus.py).  ``tables``: the records that table_out copies
+        (k_sel, sel_height - when ``cand_h[B][P][K]`` is given - and the PAL_BR_CONSENSUS bit are replaced); without them table_out is
+        None.  ``outputs``: the names of the outputs to compute (default: all that the arguments allow); the others come back as None."""
+        ck = np.ascontiguousarray(cand_k, dtype=np.int32)
+        if ck.ndim == 2:
+            ck = ck[None]
+        if ck.ndim != 3:
+            raise ValueError("cand_k must be [P][K] or [B][P][K]")
+        b, p, k = ck.shape
+        ln = consensus.check_args(b, m, k, lengths, tol, rounds)
+        if p != int(m) * (int(m) - 1) // 2:
+            raise ValueError(f"a table of {int(m)} microphones has {int(m) * (int(m) - 1) // 2} rows per frame, got {p}")
+        tab = None if tables is None else np.ascontiguousarray(tables, dtype=RECORD).reshape(b, p)
+        ch = None if cand_h is None else f64(cand_h).reshape(b, p, k)
+        if outputs is None:
+            outputs = tuple(name for name in consensus.OUTPUTS if name != "table_out" or tab is not None)
+        if not outputs or any(name not in consensus.OUTPUTS for name in outputs):
+            raise ValueError(f"outputs: at least one of {consensus.OUTPUTS}")
+        if "table_out" in outputs and tab is None:
+            raise ValueError("table_out needs the input tables")
+        shapes = {"sel": ((b, p), np.int32), "table_out": ((b, p), RECORD), "summary": ((b,), consensus.SUMMARY)}
+        out = tuple(np.zeros(*shapes[name]) if name in outputs else None for name in consensus.OUTPUTS)
+        self._check(self._lib.pal_tdoa_consensus(self._h, ptr(tab), ck.ctypes.data, ptr(ch), b, int(m), k, ln.ctypes.data, int(tol), int(rounds),
+                                                 *[ptr(a) for a in out]))
+        return out
+
+    def tdoa_consensus_dev(self, d_cand_k: int, b: int, m: int, k: int, lengths, tol: int = 1, rounds: int = 2, d_tables: int = 0,
+                           d_cand_h: int = 0, d_sel: int = 0, d_table_out: int = 0, d_summary: int = 0) -> None:
+        """Asynchronous: cand_k[b][P][k], the optional tables[b][P] / cand_h[b][P][k] and the requested outputs (0 = not wanted; at least
+        one) stay in HBM; ``lengths`` is read before the call returns.  A candidate outside 0..2 length - 2, an absent candidate 0 or a
+        gap in a pair's candidates is reported by ``synchronize``."""
+        ln = consensus.check_args(b, m, k, lengths, tol, rounds)
+        dev = [C.c_void_p(int(d)) if d else None for d in (d_tables, d_cand_k, d_cand_h, d_sel, d_table_out, d_summary)]
+        self._check(self._lib.pal_tdoa_consensus_dev(self._h, dev[0], dev[1], dev[2], int(b), int(m), int(k), ln.ctypes.data, int(tol),
+                                                     int(rounds), dev[3], dev[4], dev[5]))
 
     def solve_positions(self, tables, lengths, mic_positions, fs, c, calib_delays=None, weights="ones", buffer=5.0, grid=solve.GRID,
                         max_iter=solve.MAX_ITER, extra_starts=None, loss="linear", f_scale=1.0, return_pair_weights=False,

@@ -158,7 +158,8 @@ def host_position(table, length, mic_positions, fs, c, calib_delays, weights, cl
 
 def solve_positions_device(tables, lengths, mic_positions, fs, c, calib_delays=None, weights=None, buffer=5.0, grid=4, max_iter=200,
                            extra_starts=None, engine=None, return_records=False, clustering=("kmeans", 0.001, 2), loss="linear",
-                           f_scale=1.0, closure_tol=1, closure_min_votes=1, closure_mode="soft"):
+                           f_scale=1.0, closure_tol=1, closure_min_votes=1, closure_mode="soft", candidates=None, consensus_tol=1,
+                           consensus_rounds=2):
     """TDOA tables[B][P] (or [P]) -> positions[B][3] by the batched device solve (Engine.solve_positions; algorithm: solve.py).
     ``weights``: None / 'ones', 'snr' (the records' SNR as compute_weights weighs it) or an array [B][P].  A frame the device does
     not solve - a weight that is not finite (an infinite SNR), or no start that ended inside a stop rule - goes through the host
@@ -166,7 +167,13 @@ def solve_positions_device(tables, lengths, mic_positions, fs, c, calib_delays=N
     ``loss`` / ``f_scale``: a robust loss of solve.LOSSES for tables with outlier pairs (the host tail knows the linear one only).
     ``weights='closure'``: the loop-closure weights of the tables (Engine.tdoa_closure with ``closure_tol``, ``closure_min_votes``,
     ``closure_mode``; closure.py), computed on the device and used as the array, in the host tail too.  A frame that keeps fewer than
-    four pairs is solved like any other: its position means nothing, and ``kept_pairs`` of Engine.tdoa_closure's summary says so."""
+    four pairs is solved like any other: its position means nothing, and ``kept_pairs`` of Engine.tdoa_closure's summary says so.
+    ``candidates=(cand_k, cand_h)``: K candidate peaks per pair ([B][P][K]; cand_h may be None): the loop-closure consensus
+    (Engine.tdoa_consensus with ``consensus_tol`` and ``consensus_rounds``; consensus.py) first replaces every pair's first peak by the
+    candidate the other pairs agree with, and the solve - and the closure weights, if asked for - see the repaired tables.
+    Precondition, as for ``weights='closure'``: CENTRED indices, whose lag k - (L - 1) is the true delay.  The tables and candidates of
+    the GCC-PHAT calls keep the reference's index mapping, under which no triangle closes and the consensus moves nothing:
+    map ``tables['k_sel']`` and ``cand_k`` with ``consensus.centred`` first (tests/test_gpu_pairs_peaks.py does)."""
     from . import solve as S
     S.check_loss(loss, f_scale)
     eng = engine or default_engine()
@@ -176,6 +183,10 @@ def solve_positions_device(tables, lengths, mic_positions, fs, c, calib_delays=N
         tab = tab[None]
     w = "ones" if weights is None else weights
     ln = np.broadcast_to(np.asarray(lengths, dtype=np.int64), (tab.shape[0],))
+    if candidates is not None:
+        cand_k, cand_h = candidates
+        tab = eng.tdoa_consensus(cand_k, ln, len(mic_positions), consensus_tol, consensus_rounds, tables=tab, cand_h=cand_h,
+                                 outputs=("table_out",))[1]
     if isinstance(w, str) and w == "closure":
         w = eng.tdoa_closure(tab, ln, len(mic_positions), closure_tol, closure_min_votes, closure_mode, outputs=("weights",))[2]
     robust = {} if loss == "linear" else {"loss": loss, "f_scale": f_scale}

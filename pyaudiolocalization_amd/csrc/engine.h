@@ -98,6 +98,16 @@ constexpr Ws peak_scratch_slot(int slot) { return slot == 0 ? kWsPeaks0 : (slot 
 constexpr Ws fin_scratch_slot(int slot) { return Ws(kWsFin0 + slot); }
 constexpr Ws fin_strip_slot(int slot) { return Ws(kWsFinStrip0 + slot); }
 
+// One scratch block carved into 256-byte aligned pieces: take(bytes) is the piece's offset, `off` the block's size so far.
+struct Carve {
+  size_t off = 0;
+  size_t take(size_t bytes) {
+    const size_t at = off;
+    off = (off + bytes + 255) & ~size_t(255);
+    return at;
+  }
+};
+
 // K = num_peaks candidate peaks per pair of a batched call (pal_gcc_phat_*_peaks*): k[npairs][K] array indices, -1 past n_sel;
 // h[npairs][K] heights, +0.0 past n_sel, or nullptr
 struct CandOut {
@@ -182,6 +192,7 @@ struct Engine {
     return rc;
   }
   int status_words(int** out) { return scratch(kWsStatus, kStatusWords * sizeof(int), out); }   // peak_types.h StatusWord; zeroed when first taken
+  int upload_lengths(const int32_t* lengths, int B, void* d_dst);   // a call's frame lengths (host) -> device; the stream is synchronised behind the copy
   const cd* stage_table(int ln, bool compact = false);   // stage_tw[ln] / stage_twc[ln], made on first use (null: out of memory)
   int build_pfa(Plan& pl);                  // pfa.hip: the split of plan_geometry.h and its tables, built in pl.pfa (off if no split fits)
   void free_pfa(Pfa& f);
@@ -229,6 +240,8 @@ struct Engine {
   int tdoa_closure_dev(const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, int32_t tol, int32_t min_votes, int32_t weight_mode,
                        int32_t* d_votes, int32_t* d_mic_closed, double* d_weights, pal_closure_frame* d_summary);
   int closure_check(int B, int M, const int32_t* lengths, int32_t tol, int32_t min_votes, int32_t weight_mode);
+  int lag_votes(const int32_t* d_lag, int B, int M, int tol, int32_t* d_votes);   // k_closure_votes on B lag matrices [M][M] -> votes [B][P]
+  int frames_check(const char* what, int B, int M, const int32_t* lengths, int32_t tol);   // the checks closure_check and consensus_check share
   // consensus.hip: loop-closure consensus over K candidates per pair (every pointer but `lengths` in HBM, each output or nullptr); asynchronous
   int tdoa_consensus_dev(const pal_pair_record* d_tables, const int32_t* d_cand_k, const double* d_cand_h, int B, int M, int K,
                          const int32_t* lengths, int32_t tol, int32_t rounds, int32_t* d_sel, pal_pair_record* d_table_out,

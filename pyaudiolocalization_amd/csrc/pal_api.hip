@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "closure_tiles.h"
 #include "engine.h"
 
 namespace pal {
@@ -44,6 +45,12 @@ int Engine::scratch(Ws idx, size_t bytes, void** out) {
   }
   *out = ws[idx];
   return PAL_OK;
+}
+
+// `lengths` is host memory: the copy has left it when this returns
+int Engine::upload_lengths(const int32_t* lengths, int B, void* d_dst) {
+  PAL_HIP(hipMemcpyAsync(d_dst, lengths, size_t(B) * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  return check(hipStreamSynchronize(stream), "lengths upload");
 }
 
 // ---- profiling: one event pair per launch, resolved after the stream drains ----
@@ -174,7 +181,7 @@ static void build_quads_blocked(int B, int M, int blk, std::vector<int4>& q, std
             int4& t = q[size_t(k / 2)];
             if (k & 1) { t.z = b * M + i; t.w = b * M + j; }
             else { t.x = b * M + i; t.y = b * M + j; }
-            perm[size_t(k)] = int(int64_t(b) * P + int64_t(i) * M - int64_t(i) * (i + 1) / 2 + (j - i - 1));
+            perm[size_t(k)] = int(int64_t(b) * P + pair_row(int64_t(i), int64_t(M)) + j);
           }
 }
 
@@ -630,15 +637,13 @@ int pal_tdoa_closure(pal_handle h, const pal_pair_record* tables, int B, int M, 
       return e->fail(PAL_ERR_INVALID, "frame %d, pair %d: k_sel %d outside 0..%d", int(r / P), int(r % P), int(k), int(2 * len - 2));
   }
   // staged outputs in one block: [votes | mic_closed | weights | summary]
-  auto align = [](size_t v) { return (v + 255) & ~size_t(255); };
-  const size_t o_votes = 0, o_mic = align(votes ? np * sizeof(int32_t) : 0);
-  const size_t o_wt = o_mic + align(mic_closed ? size_t(B) * M * sizeof(int32_t) : 0);
-  const size_t o_sum = o_wt + align(weights ? np * sizeof(double) : 0);
-  const size_t total = o_sum + align(summary ? size_t(B) * sizeof(pal_closure_frame) : 0);
+  Carve c;
+  const size_t o_votes = c.take(votes ? np * sizeof(int32_t) : 0), o_mic = c.take(mic_closed ? size_t(B) * M * sizeof(int32_t) : 0);
+  const size_t o_wt = c.take(weights ? np * sizeof(double) : 0), o_sum = c.take(summary ? size_t(B) * sizeof(pal_closure_frame) : 0);
   void* dt = nullptr;
   char* out = nullptr;
   PAL_TRY(e->scratch(kWsStageTable, np * sizeof(pal_pair_record), &dt));
-  PAL_TRY(e->scratch(kWsStageOut, total, &out));
+  PAL_TRY(e->scratch(kWsStageOut, c.off, &out));
   PAL_TRY(e->check(hipMemcpyAsync(dt, tables, np * sizeof(pal_pair_record), hipMemcpyHostToDevice, e->stream), "tables upload"));
   int32_t* dv = votes ? reinterpret_cast<int32_t*>(out + o_votes) : nullptr;
   int32_t* dm = mic_closed ? reinterpret_cast<int32_t*>(out + o_mic) : nullptr;
@@ -684,26 +689,25 @@ int pal_tdoa_consensus(pal_handle h, const pal_pair_record* tables, const int32_
     }
   }
   // staged inputs [cand_k | cand_h] and outputs [sel | table_out | summary], one block each
-  auto align = [](size_t v) { return (v + 255) & ~size_t(255); };
   const size_t nc = np * size_t(K);
-  const size_t o_h = align(nc * sizeof(int32_t)), in_total = o_h + align(cand_h ? nc * sizeof(double) : 0);
-  const size_t o_tab = align(sel ? np * sizeof(int32_t) : 0);
-  const size_t o_sum = o_tab + align(table_out ? np * sizeof(pal_pair_record) : 0);
-  const size_t total = o_sum + align(summary ? size_t(B) * sizeof(pal_consensus_frame) : 0);
+  Carve ci, co;
+  const size_t o_k = ci.take(nc * sizeof(int32_t)), o_h = ci.take(cand_h ? nc * sizeof(double) : 0);
+  const size_t o_sel = co.take(sel ? np * sizeof(int32_t) : 0), o_tab = co.take(table_out ? np * sizeof(pal_pair_record) : 0);
+  const size_t o_sum = co.take(summary ? size_t(B) * sizeof(pal_consensus_frame) : 0);
   void* dt = nullptr;
   char *in = nullptr, *out = nullptr;
   if (tables) {
     PAL_TRY(e->scratch(kWsStageTable, np * sizeof(pal_pair_record), &dt));
     PAL_TRY(e->check(hipMemcpyAsync(dt, tables, np * sizeof(pal_pair_record), hipMemcpyHostToDevice, e->stream), "tables upload"));
   }
-  PAL_TRY(e->scratch(kWsStageIn, in_total, &in));
-  PAL_TRY(e->scratch(kWsStageOut, total, &out));
-  PAL_TRY(e->check(hipMemcpyAsync(in, cand_k, nc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream), "candidates upload"));
+  PAL_TRY(e->scratch(kWsStageIn, ci.off, &in));
+  PAL_TRY(e->scratch(kWsStageOut, co.off, &out));
+  PAL_TRY(e->check(hipMemcpyAsync(in + o_k, cand_k, nc * sizeof(int32_t), hipMemcpyHostToDevice, e->stream), "candidates upload"));
   if (cand_h) PAL_TRY(e->check(hipMemcpyAsync(in + o_h, cand_h, nc * sizeof(double), hipMemcpyHostToDevice, e->stream), "heights upload"));
-  int32_t* ds = sel ? reinterpret_cast<int32_t*>(out) : nullptr;
+  int32_t* ds = sel ? reinterpret_cast<int32_t*>(out + o_sel) : nullptr;
   pal_pair_record* dto = table_out ? reinterpret_cast<pal_pair_record*>(out + o_tab) : nullptr;
   pal_consensus_frame* dsum = summary ? reinterpret_cast<pal_consensus_frame*>(out + o_sum) : nullptr;
-  PAL_TRY(e->tdoa_consensus_dev(static_cast<const pal_pair_record*>(dt), reinterpret_cast<const int32_t*>(in),
+  PAL_TRY(e->tdoa_consensus_dev(static_cast<const pal_pair_record*>(dt), reinterpret_cast<const int32_t*>(in + o_k),
                                 cand_h ? reinterpret_cast<const double*>(in + o_h) : nullptr, B, M, K, lengths, tol, rounds, ds, dto, dsum));
   if (sel) PAL_TRY(e->check(hipMemcpyAsync(sel, ds, np * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "sel download"));
   if (table_out) PAL_TRY(e->check(hipMemcpyAsync(table_out, dto, np * sizeof(pal_pair_record), hipMemcpyDeviceToHost, e->stream), "table download"));

@@ -311,8 +311,6 @@ __global__ __launch_bounds__(kWeightThreads) void k_solve_weights(SolveArgs a) {
   }
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
-
 int Engine::solve_positions_dev(const pal_pair_record* d_tables, int B, int M, const int32_t* lengths, const double* mics, const double* calib,
                                 const double* weights, const double* extra_starts, const pal_solve_params* prm, pal_position_record* out) {
   return solve_positions_impl(d_tables, B, M, lengths, mics, calib, weights, extra_starts, prm, out, sv::kLossLinear, 1.0, nullptr);
@@ -368,18 +366,17 @@ int Engine::solve_positions_impl(const pal_pair_record* d_tables, int B, int M, 
   const bool want_pw = loss != sv::kLossLinear && pair_weights;
   // one scratch block: [lengths | mics | calib | weights | extra | bw | v | starts | frames | results | out | pair weights]
   const size_t np = size_t(B) * size_t(P);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off = align256(off + bytes); return at; };
-  const size_t o_len = take(size_t(B) * sizeof(int32_t)), o_mic = take(size_t(M) * 3 * sizeof(double));
-  const size_t o_cal = take(calib ? size_t(M) * sizeof(double) : 0);
-  const size_t o_wt = take(prm->weight_mode == PAL_SOLVE_W_ARRAY ? np * sizeof(double) : 0);
-  const size_t o_ex = take(size_t(B) * size_t(prm->n_extra) * 3 * sizeof(double));
-  const size_t o_bw = take(np * sizeof(double2)), o_v = take(np * sizeof(double));
-  const size_t o_st = take(size_t(B) * S * 3 * sizeof(double)), o_fr = take(size_t(B) * sizeof(SolveFrame));
-  const size_t o_res = take(size_t(B) * S * sizeof(SolveStart)), o_out = take(size_t(B) * sizeof(pal_position_record));
-  const size_t o_pw = take(want_pw ? np * sizeof(double) : 0);
+  Carve cv;
+  const size_t o_len = cv.take(size_t(B) * sizeof(int32_t)), o_mic = cv.take(size_t(M) * 3 * sizeof(double));
+  const size_t o_cal = cv.take(calib ? size_t(M) * sizeof(double) : 0);
+  const size_t o_wt = cv.take(prm->weight_mode == PAL_SOLVE_W_ARRAY ? np * sizeof(double) : 0);
+  const size_t o_ex = cv.take(size_t(B) * size_t(prm->n_extra) * 3 * sizeof(double));
+  const size_t o_bw = cv.take(np * sizeof(double2)), o_v = cv.take(np * sizeof(double));
+  const size_t o_st = cv.take(size_t(B) * S * 3 * sizeof(double)), o_fr = cv.take(size_t(B) * sizeof(SolveFrame));
+  const size_t o_res = cv.take(size_t(B) * S * sizeof(SolveStart)), o_out = cv.take(size_t(B) * sizeof(pal_position_record));
+  const size_t o_pw = cv.take(want_pw ? np * sizeof(double) : 0);
   char* base = nullptr;
-  PAL_TRY(scratch(kWsSolve, off, &base));
+  PAL_TRY(scratch(kWsSolve, cv.off, &base));
   PAL_HIP(hipMemcpyAsync(base + o_len, lengths, size_t(B) * sizeof(int32_t), hipMemcpyHostToDevice, stream));
   PAL_HIP(hipMemcpyAsync(base + o_mic, mics, size_t(M) * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
   if (calib) PAL_HIP(hipMemcpyAsync(base + o_cal, calib, size_t(M) * sizeof(double), hipMemcpyHostToDevice, stream));

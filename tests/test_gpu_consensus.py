@@ -137,6 +137,21 @@ def test_every_subset_of_outputs_and_optional_inputs(engine):
         _assert_same(form(engine, cand, ln, 17, 1, 2, None, None, outputs=("sel", "summary")), want, (form.__name__, "no tables"))
 
 
+def test_the_summary_votes_are_closure_launches(engine):
+    """A call with a summary takes the closure votes of candidate 0 and of the result from k_closure_votes (two launches) and runs
+    k_consensus_round exactly ``rounds`` times; a call without one launches no k_closure_votes."""
+    cand, ln, tab, heights = _frames(17, 2, 2, FIVE_LENGTHS[:2])
+    want = _want(cand, ln, 17, 1, 2, tab, heights)
+    for outputs, votes_launches in ((CN.OUTPUTS, 2), (("sel", "table_out"), 0)):
+        engine.profile_begin()
+        got = _dev(engine, cand, ln, 17, 1, 2, tab, heights, outputs=outputs)
+        engine.profile_end()
+        launches = {name: v[1] for name, v in engine.profile_entries().items()}
+        assert launches.get("k_closure_votes", 0) == votes_launches, (outputs, launches)
+        assert launches.get("k_consensus_round", 0) == 2, (outputs, launches)
+        _assert_same(got, want, outputs)
+
+
 def test_a_frame_alone_and_in_a_batch(engine):
     cand, ln, tab, heights = _frames(33, 4, 5, FIVE_LENGTHS)
     batch = _dev(engine, cand, ln, 33, 1, 2, tab, heights)

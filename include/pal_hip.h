@@ -298,6 +298,72 @@ int pal_tdoa_consensus(pal_handle h, const pal_pair_record* tables, const int32_
                        const int32_t* lengths, int32_t tol, int32_t rounds, int32_t* sel, pal_pair_record* table_out,
                        pal_consensus_frame* summary);
 
+/* ---- steered-response power (SRP-PHAT) map from all-pairs rows (no counterpart in the reference) ---------------
+ * For every cell of a grid the map sums, over all pairs, the pair's GCC-PHAT row at the lag the cell's centre predicts: no peak is
+ * picked per pair, the table's index mapping plays no part, and several sources show as several maxima.
+ * pyaudiolocalization_amd/srp.py states every rule below sample by sample; csrc/srp_math.h is the arithmetic for host and device.
+ * Conventions: the row of pair (i, j), i < j, has n = 2L - 1 samples with zero lag at index 0 and peaks at the circular lag d_i - d_j;
+ * everything here counts the centred lag s = d_j - d_i in samples (the sign of the closure check): raw[u] = row[(-u) mod n].
+ *
+ * pal_gcc_phat_all_pairs_strips*: frames[B][M][L] -> strips[B][P][2T+1] (P = M(M-1)/2, row-major i<j) with
+ *     strips[..][p][T + s] = sum over u = -W..W of (W + 1 - |u|) * raw_p[s + u]   (increasing u, every product rounded, no fma):
+ *   the rows' samples around zero lag, smoothed by a triangle of half-width W (W = 0: the samples themselves).  `table` (may be NULL)
+ *   receives the one-peak table of the same rows, as pal_gcc_phat_all_pairs with corr gives it (prm: as there, num_peaks = 1).  The
+ *   rows go through engine scratch in slices of whole frames that stay under about 1 GiB where one frame does (one frame of 64
+ *   microphones and L = 44 100 alone is 1.4 GB of rows: a slice is never less than one frame).
+ *   B >= 1, M >= 2, T >= 0, 0 <= W <= 32, T + W <= L - 1: PAL_ERR_INVALID otherwise.
+ *
+ * pal_srp_map*: strips[B][P][2T+1] -> power[B][G] over the grid's G = count[0] * count[1] * count[2] cells; cell (ix, iy, iz) has the
+ *   linear index g = (ix * count[1] + iy) * count[2] + iz and the centre lo[a] + (i_a + 0.5) * ((hi[a] - lo[a]) / count[a]).
+ *     power[g] = sum over p of w_p * strips[p][T + s(g, p)],   s(g, p) = rint(((d_j - d_i) * fs) / c)   (half to even)
+ *   with d_m the distance of the centre from microphone m (q = dx*dx; q += dy*dy; q += dz*dz; sqrt(q), every product rounded) and
+ *   w_p = pair_weights[b][p], or 1 when pair_weights is NULL.  A term with |s| > T is clipped: it adds nothing and is counted in
+ *   summary[b].clipped.  The order of the sum is fixed: the same input gives the same bytes whatever B is.  mics[M][3] and the grid
+ *   are host memory, read before the call returns.  With K > 0 the first K peaks of every frame's map go to peaks[B][K] (see
+ *   pal_srp_peaks).  power, peaks and summary may each be NULL, not all of them; peaks needs K > 0.
+ *   1 <= count[a] <= 1024 (PAL_ERR_INVALID below 1, PAL_ERR_UNSUPPORTED above), G <= 2^24 (PAL_ERR_UNSUPPORTED), hi[a] > lo[a], all
+ *   coordinates finite, fs > 0, c > 0, 0 <= K <= PAL_SRP_MAX_PEAKS, 1 <= R <= PAL_SRP_MAX_RADIUS when K > 0, T >= 0, M >= 2, B >= 1.
+ *
+ * pal_srp_peaks*: power[B][G] -> peaks[B][K].  A cell is a peak iff it is not NaN and no cell of its (2R+1)^3 neighbourhood, cut at
+ *   the grid's border, is higher or is equal with a lower linear index.  The peaks are ordered by power descending, then by index;
+ *   the first K are written, absent entries as index -1 and all else 0.  summary (may be NULL): n_peaks = entries present, clipped = 0.
+ *   1 <= K <= PAL_SRP_MAX_PEAKS, 1 <= R <= PAL_SRP_MAX_RADIUS.
+ *
+ * The _dev forms are asynchronous on the engine's stream (results complete after pal_synchronize); every `d_` pointer comes from
+ * pal_device_alloc.  Every argument check is made before any buffer is touched. */
+#define PAL_SRP_MAX_SMOOTH 32
+#define PAL_SRP_MAX_PEAKS 8
+#define PAL_SRP_MAX_RADIUS 4
+typedef struct pal_srp_grid {    /* 64 bytes */
+  double lo[3], hi[3];    /* the box                                                               */
+  int32_t count[3];       /* cells per axis                                                        */
+  int32_t reserved;
+} pal_srp_grid;
+typedef struct pal_srp_peak {    /* 40 bytes */
+  double x, y, z;         /* the cell's centre                                                     */
+  double power;           /* the map at that cell                                                  */
+  int32_t index;          /* its linear index, -1 = absent                                         */
+  int32_t reserved;
+} pal_srp_peak;
+typedef struct pal_srp_frame {   /* 16 bytes */
+  int64_t clipped;        /* terms of the map's sums with |s| > T                                  */
+  int32_t n_peaks;        /* entries present in the frame's peaks                                  */
+  int32_t reserved;
+} pal_srp_frame;
+int pal_gcc_phat_all_pairs_strips_dev(pal_handle h, const double* d_frames, int B, int M, int L, const pal_phat_params* prm, int T, int W,
+                                      pal_pair_record* d_table, double* d_strips);
+int pal_gcc_phat_all_pairs_strips(pal_handle h, const double* frames, int B, int M, int L, const pal_phat_params* prm, int T, int W,
+                                  pal_pair_record* table, double* strips);
+int pal_srp_map_dev(pal_handle h, const double* d_strips, int B, int M, int T, const double* mics, double fs, double c,
+                    const pal_srp_grid* grid, const double* d_pair_weights, int K, int R, double* d_power, pal_srp_peak* d_peaks,
+                    pal_srp_frame* d_summary);
+int pal_srp_map(pal_handle h, const double* strips, int B, int M, int T, const double* mics, double fs, double c, const pal_srp_grid* grid,
+                const double* pair_weights, int K, int R, double* power, pal_srp_peak* peaks, pal_srp_frame* summary);
+int pal_srp_peaks_dev(pal_handle h, const double* d_power, int B, const pal_srp_grid* grid, int K, int R, pal_srp_peak* d_peaks,
+                      pal_srp_frame* d_summary);
+int pal_srp_peaks(pal_handle h, const double* power, int B, const pal_srp_grid* grid, int K, int R, pal_srp_peak* peaks,
+                  pal_srp_frame* summary);
+
 /* single-pair signatures: phat_correlation(sig1, sig2) (utils.py:108) -> corr[n1+n2-1] */
 int pal_phat_correlation(pal_handle h, const double* sig1, int n1, const double* sig2, int n2, double* corr);
 /* get_time_delays_phat (utils.py:121): corr[n1+n2-1] (may be NULL), k_out[num_peaks] array indices */

@@ -32,6 +32,17 @@ class SolveParams(C.Structure):
                 ("weight_mode", C.c_int32), ("n_extra", C.c_int32)]
 
 
+class SrpGrid(C.Structure):                                             # pal_srp_grid, 64 bytes
+    _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("count", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(SrpGrid) == 64
+# pal_srp_peak (40 bytes) and pal_srp_frame (16 bytes)
+SRP_PEAK = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("power", "<f8"), ("index", "<i4"), ("reserved", "<i4")])
+SRP_FRAME = np.dtype([("clipped", "<i8"), ("n_peaks", "<i4"), ("reserved", "<i4")])
+assert SRP_PEAK.itemsize == 40 and SRP_FRAME.itemsize == 16
+SRP_MAX_SMOOTH, SRP_MAX_PEAKS, SRP_MAX_RADIUS = 32, 8, 4
+
 # one row of the TDOA table (pal_pair_record, 48 bytes)
 RECORD = np.dtype([("k_sel", "<i4"), ("branch", "<i4"), ("k_argmax", "<i4"), ("n_sel", "<i4"),
                    ("cmax", "<f8"), ("cmin", "<f8"), ("snr", "<f8"), ("sel_height", "<f8")])
@@ -98,6 +109,16 @@ SIGNATURES = {
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "pal_tdoa_consensus": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pal_gcc_phat_all_pairs_strips_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(PhatParams), C.c_int, C.c_int,
+                                                    C.c_void_p, C.c_void_p]),
+    "pal_gcc_phat_all_pairs_strips": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(PhatParams), C.c_int, C.c_int,
+                                                C.c_void_p, C.c_void_p]),
+    "pal_srp_map_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.POINTER(SrpGrid),
+                                  C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pal_srp_map": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.POINTER(SrpGrid),
+                              C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pal_srp_peaks_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(SrpGrid), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pal_srp_peaks": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(SrpGrid), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pal_phat_correlation": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "pal_get_time_delays_phat": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(PhatParams), C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

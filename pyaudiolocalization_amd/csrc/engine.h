@@ -92,7 +92,8 @@ enum Ws : int {
   kWsFinStrip0 = 26, kWsFinStrip1 = 27, kWsFinStrip2 = 28,   // its SNR strips (pair_route.h fin_strip) per stream slot, see fin_strip_slot
   kWsConsensus = 29,   // the consensus (consensus.hip): frame lengths, candidate cubes, chosen-lag matrices, three selections, two vote tables
   kWsCandK = 30, kWsCandH = 31,   // the selected peaks of a launch group per stream slot (PAL_MAX_PEAKS indices / heights per row), compacted into a CandOut
-  kWsCount = 32
+  kWsSrp = 32,         // the SRP map (srp.hip): a frame slice's correlation rows and one-peak table, microphones, clip counters, peak marks, the map when the caller takes none
+  kWsCount = 33
 };
 constexpr Ws peak_scratch_slot(int slot) { return slot == 0 ? kWsPeaks0 : (slot == 1 ? kWsPeaks1 : kWsPeaks2); }
 constexpr Ws fin_scratch_slot(int slot) { return Ws(kWsFin0 + slot); }
@@ -247,6 +248,16 @@ struct Engine {
                          const int32_t* lengths, int32_t tol, int32_t rounds, int32_t* d_sel, pal_pair_record* d_table_out,
                          pal_consensus_frame* d_summary);
   int consensus_check(int B, int M, int K, const int32_t* lengths, int32_t tol, int32_t rounds);
+  // srp.hip: lag strips of stored rows, the steered-response power map and its peaks (every pointer but `mics` and `grid` in HBM, each
+  // output or nullptr); asynchronous.  The *_check functions hold the argument checks that the host and the _dev forms share.
+  int srp_strips_check(int B, int M, int L, int T, int W);
+  int srp_strips_rows(const double* d_rows, int64_t nrows, int L, int T, int W, double* d_strips);   // k_srp_strips on rows[nrows][2L-1]
+  int srp_map_check(int B, int M, int T, const double* mics, double fs, double c, const pal_srp_grid* grid, int K, int R, bool any_output,
+                    bool peaks_out);
+  int srp_map_dev(const double* d_strips, int B, int M, int T, const double* mics, double fs, double c, const pal_srp_grid* grid,
+                  const double* d_pair_weights, int K, int R, double* d_power, pal_srp_peak* d_peaks, pal_srp_frame* d_summary);
+  int srp_peaks_check(int B, const pal_srp_grid* grid, int K, int R);
+  int srp_peaks_dev(const double* d_power, int B, const pal_srp_grid* grid, int K, int R, pal_srp_peak* d_peaks, pal_srp_frame* d_summary);
   int32_t* solve_idx = nullptr;    // device table pair -> i | j << 16 of the last microphone count
   int solve_idx_M = 0;
   // resample.hip: the right wing of the interpolation filter as pal_resample_set_filter received it, and the ratio whose scaled

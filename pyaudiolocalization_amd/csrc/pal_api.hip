@@ -245,6 +245,33 @@ static int all_pairs_dev(Engine* e, const double* d_frames, int B, int M, int L,
   return e->pair_correlations(*pl, spectra, rows, static_cast<const int4*>(qp), np, L, *prm, d_table, nullptr, d_corr, nonzero, false, cands);
 }
 
+// Lag strips of every pair's row (srp.hip): the frames go through the pair pipeline in slices of whole frames whose rows
+// [slice pairs][2L-1] sit in engine scratch - about 1 GiB where one frame's rows are less, otherwise one frame - and k_srp_strips cuts
+// each slice's strips behind it on `stream` (the pipeline's side streams start behind `stream` and are joined into it, so a slice's rows
+// are complete before they are read and read before the next slice overwrites them).  d_table (or nullptr): the one-peak table.
+static int strips_dev(Engine* e, const double* d_frames, int B, int M, int L, const pal_phat_params* prm, int T, int W,
+                      pal_pair_record* d_table, double* d_strips) {
+  PAL_TRY(validate(e, prm));
+  PAL_TRY(e->srp_strips_check(B, M, L, T, W));
+  if (prm->num_peaks != 1) return e->fail(PAL_ERR_INVALID, "the strips call carries the one-peak table: num_peaks must be 1");
+  const size_t P = size_t(M) * size_t(M - 1) / 2, n = size_t(2 * L - 1);
+  const size_t frame_bytes = P * n * sizeof(double);
+  const size_t fit = (size_t(1) << 30) / frame_bytes;
+  const int per = int(fit < 1 ? 1 : (fit > size_t(B) ? size_t(B) : fit));
+  Carve c;
+  const size_t o_rows = c.take(size_t(per) * frame_bytes), o_tab = c.take(d_table ? 0 : size_t(per) * P * sizeof(pal_pair_record));
+  char* base = nullptr;
+  PAL_TRY(e->scratch(kWsSrp, c.off, &base));
+  double* rows = reinterpret_cast<double*>(base + o_rows);
+  for (int f0 = 0; f0 < B; f0 += per) {
+    const int nb = B - f0 < per ? B - f0 : per;
+    pal_pair_record* tab = d_table ? d_table + size_t(f0) * P : reinterpret_cast<pal_pair_record*>(base + o_tab);
+    PAL_TRY(all_pairs_dev(e, d_frames + size_t(f0) * size_t(M) * size_t(L), nb, M, L, prm, tab, rows));
+    PAL_TRY(e->srp_strips_rows(rows, int64_t(nb) * int64_t(P), L, T, W, d_strips + size_t(f0) * P * size_t(2 * T + 1)));
+  }
+  return PAL_OK;
+}
+
 // explicit pair list over R equal-length rows (host buffers): upload, then the device-resident form
 static int pairs_host(Engine* e, const double* rows_in, int R, int L, const int32_t* pairs, int64_t P,
                       const pal_phat_params* prm, pal_pair_record* table) {
@@ -712,6 +739,97 @@ int pal_tdoa_consensus(pal_handle h, const pal_pair_record* tables, const int32_
   if (sel) PAL_TRY(e->check(hipMemcpyAsync(sel, ds, np * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "sel download"));
   if (table_out) PAL_TRY(e->check(hipMemcpyAsync(table_out, dto, np * sizeof(pal_pair_record), hipMemcpyDeviceToHost, e->stream), "table download"));
   if (summary) PAL_TRY(e->check(hipMemcpyAsync(summary, dsum, size_t(B) * sizeof(pal_consensus_frame), hipMemcpyDeviceToHost, e->stream), "summary download"));
+  return pal_synchronize(h);
+}
+
+// ---- steered-response power map (srp.hip): lag strips of all pairs, the map over a grid, the map's peaks ----
+int pal_gcc_phat_all_pairs_strips_dev(pal_handle h, const double* d_frames, int B, int M, int L, const pal_phat_params* prm, int T, int W,
+                                      pal_pair_record* d_table, double* d_strips) {
+  ENGINE(h);
+  if (!d_frames || !d_strips) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  return strips_dev(e, d_frames, B, M, L, prm, T, W, d_table, d_strips);
+}
+
+int pal_gcc_phat_all_pairs_strips(pal_handle h, const double* frames, int B, int M, int L, const pal_phat_params* prm, int T, int W,
+                                  pal_pair_record* table, double* strips) {
+  ENGINE(h);
+  if (!frames || !strips) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  PAL_TRY(validate(e, prm));
+  PAL_TRY(e->srp_strips_check(B, M, L, T, W));
+  if (prm->num_peaks != 1) return e->fail(PAL_ERR_INVALID, "the strips call carries the one-peak table: num_peaks must be 1");
+  const size_t fbytes = size_t(B) * M * L * sizeof(double);
+  const size_t np = size_t(B) * (size_t(M) * size_t(M - 1) / 2), sbytes = np * size_t(2 * T + 1) * sizeof(double);
+  void *df = nullptr, *dt = nullptr, *ds = nullptr;
+  PAL_TRY(e->scratch(kWsStageIn, fbytes, &df));
+  if (table) PAL_TRY(e->scratch(kWsStageTable, np * sizeof(pal_pair_record), &dt));
+  PAL_TRY(e->scratch(kWsStageOut, sbytes, &ds));
+  PAL_TRY(e->check(hipMemcpyAsync(df, frames, fbytes, hipMemcpyHostToDevice, e->stream), "frames upload"));
+  PAL_TRY(strips_dev(e, static_cast<const double*>(df), B, M, L, prm, T, W, static_cast<pal_pair_record*>(dt), static_cast<double*>(ds)));
+  if (table) PAL_TRY(e->check(hipMemcpyAsync(table, dt, np * sizeof(pal_pair_record), hipMemcpyDeviceToHost, e->stream), "table download"));
+  PAL_TRY(e->check(hipMemcpyAsync(strips, ds, sbytes, hipMemcpyDeviceToHost, e->stream), "strips download"));
+  return pal_synchronize(h);
+}
+
+int pal_srp_map_dev(pal_handle h, const double* d_strips, int B, int M, int T, const double* mics, double fs, double c,
+                    const pal_srp_grid* grid, const double* d_pair_weights, int K, int R, double* d_power, pal_srp_peak* d_peaks,
+                    pal_srp_frame* d_summary) {
+  ENGINE(h);
+  return e->srp_map_dev(d_strips, B, M, T, mics, fs, c, grid, d_pair_weights, K, R, d_power, d_peaks, d_summary);
+}
+
+int pal_srp_map(pal_handle h, const double* strips, int B, int M, int T, const double* mics, double fs, double c, const pal_srp_grid* grid,
+                const double* pair_weights, int K, int R, double* power, pal_srp_peak* peaks, pal_srp_frame* summary) {
+  ENGINE(h);
+  PAL_TRY(e->srp_map_check(B, M, T, mics, fs, c, grid, K, R, power || peaks || summary, peaks != nullptr));
+  if (!strips) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  const size_t P = size_t(M) * size_t(M - 1) / 2, np = size_t(B) * P;
+  const size_t G = size_t(grid->count[0]) * size_t(grid->count[1]) * size_t(grid->count[2]);
+  // staged inputs [strips | pair_weights] and outputs [power | peaks | summary], one block each
+  Carve ci, co;
+  const size_t sbytes = np * size_t(2 * T + 1) * sizeof(double);
+  const size_t o_st = ci.take(sbytes), o_w = ci.take(pair_weights ? np * sizeof(double) : 0);
+  const size_t o_pw = co.take(power ? size_t(B) * G * sizeof(double) : 0), o_pk = co.take(peaks ? size_t(B) * size_t(K) * sizeof(pal_srp_peak) : 0);
+  const size_t o_sum = co.take(summary ? size_t(B) * sizeof(pal_srp_frame) : 0);
+  char *in = nullptr, *out = nullptr;
+  PAL_TRY(e->scratch(kWsStageIn, ci.off, &in));
+  PAL_TRY(e->scratch(kWsStageOut, co.off, &out));
+  PAL_TRY(e->check(hipMemcpyAsync(in + o_st, strips, sbytes, hipMemcpyHostToDevice, e->stream), "strips upload"));
+  if (pair_weights) PAL_TRY(e->check(hipMemcpyAsync(in + o_w, pair_weights, np * sizeof(double), hipMemcpyHostToDevice, e->stream), "weights upload"));
+  double* dpw = power ? reinterpret_cast<double*>(out + o_pw) : nullptr;
+  pal_srp_peak* dpk = peaks ? reinterpret_cast<pal_srp_peak*>(out + o_pk) : nullptr;
+  pal_srp_frame* dsum = summary ? reinterpret_cast<pal_srp_frame*>(out + o_sum) : nullptr;
+  PAL_TRY(e->srp_map_dev(reinterpret_cast<const double*>(in + o_st), B, M, T, mics, fs, c, grid,
+                         pair_weights ? reinterpret_cast<const double*>(in + o_w) : nullptr, K, R, dpw, dpk, dsum));
+  if (power) PAL_TRY(e->check(hipMemcpyAsync(power, dpw, size_t(B) * G * sizeof(double), hipMemcpyDeviceToHost, e->stream), "map download"));
+  if (peaks) PAL_TRY(e->check(hipMemcpyAsync(peaks, dpk, size_t(B) * size_t(K) * sizeof(pal_srp_peak), hipMemcpyDeviceToHost, e->stream), "peaks download"));
+  if (summary) PAL_TRY(e->check(hipMemcpyAsync(summary, dsum, size_t(B) * sizeof(pal_srp_frame), hipMemcpyDeviceToHost, e->stream), "summary download"));
+  return pal_synchronize(h);
+}
+
+int pal_srp_peaks_dev(pal_handle h, const double* d_power, int B, const pal_srp_grid* grid, int K, int R, pal_srp_peak* d_peaks,
+                      pal_srp_frame* d_summary) {
+  ENGINE(h);
+  return e->srp_peaks_dev(d_power, B, grid, K, R, d_peaks, d_summary);
+}
+
+int pal_srp_peaks(pal_handle h, const double* power, int B, const pal_srp_grid* grid, int K, int R, pal_srp_peak* peaks,
+                  pal_srp_frame* summary) {
+  ENGINE(h);
+  PAL_TRY(e->srp_peaks_check(B, grid, K, R));
+  if (!power || !peaks) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  const size_t G = size_t(grid->count[0]) * size_t(grid->count[1]) * size_t(grid->count[2]);
+  Carve co;
+  const size_t o_pk = co.take(size_t(B) * size_t(K) * sizeof(pal_srp_peak)), o_sum = co.take(summary ? size_t(B) * sizeof(pal_srp_frame) : 0);
+  void* in = nullptr;
+  char* out = nullptr;
+  PAL_TRY(e->scratch(kWsStageIn, size_t(B) * G * sizeof(double), &in));
+  PAL_TRY(e->scratch(kWsStageOut, co.off, &out));
+  PAL_TRY(e->check(hipMemcpyAsync(in, power, size_t(B) * G * sizeof(double), hipMemcpyHostToDevice, e->stream), "map upload"));
+  pal_srp_peak* dpk = reinterpret_cast<pal_srp_peak*>(out + o_pk);
+  pal_srp_frame* dsum = summary ? reinterpret_cast<pal_srp_frame*>(out + o_sum) : nullptr;
+  PAL_TRY(e->srp_peaks_dev(static_cast<const double*>(in), B, grid, K, R, dpk, dsum));
+  PAL_TRY(e->check(hipMemcpyAsync(peaks, dpk, size_t(B) * size_t(K) * sizeof(pal_srp_peak), hipMemcpyDeviceToHost, e->stream), "peaks download"));
+  if (summary) PAL_TRY(e->check(hipMemcpyAsync(summary, dsum, size_t(B) * sizeof(pal_srp_frame), hipMemcpyDeviceToHost, e->stream), "summary download"));
   return pal_synchronize(h);
 }
 

@@ -1,0 +1,108 @@
+// srp_math.h - the arithmetic of the steered-response power map (srp.hip; specification: pyaudiolocalization_amd/srp.py) for host and
+// device: the grid point, the distance, the lag with its clip test, the smoothing sum of a lag strip and the neighbourhood rule of the
+// map's peaks.  Every function gives the specification's bits, so it is compiled with -ffp-contract=off wherever it is used: a product
+// is rounded before it is added.  No HIP runtime calls; tests/host/test_srp_math.cpp runs it on the CPU against srp.py.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#include <hip/hip_runtime.h>
+#define PAL_SRP_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define PAL_SRP_HD inline
+#endif
+
+namespace pal {
+
+constexpr int kSrpMaxSmooth = 32;        // largest half-width W of the triangular smoothing
+constexpr int kSrpMaxCount = 1024;       // cells per axis
+constexpr int64_t kSrpMaxCells = int64_t(1) << 24;
+constexpr int kSrpMaxPeaks = 8, kSrpMaxRadius = 4;
+
+// correctly rounded square root and quotient.  Device: __dsqrt_rn and __ddiv_rn are the IEEE forms whatever the file's flags say (the
+// plain operators are the same under the default flags; these do not change with -ffast-math style options); host: the C++ operators.
+PAL_SRP_HD double srp_sqrt(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __dsqrt_rn(x);
+#else
+  return std::sqrt(x);
+#endif
+}
+PAL_SRP_HD double srp_div(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __ddiv_rn(a, b);
+#else
+  return a / b;
+#endif
+}
+
+// cell size of one axis, and the centre of cell i: lo + (i + 0.5) * step in that order
+PAL_SRP_HD double srp_step(double lo, double hi, int count) { return srp_div(hi - lo, double(count)); }
+PAL_SRP_HD double srp_coord(double lo, double step, int i) { return lo + (double(i) + 0.5) * step; }
+
+// g = (ix * ny + iy) * nz + iz
+PAL_SRP_HD void srp_cell(int g, int ny, int nz, int& ix, int& iy, int& iz) {
+  iz = g % nz;
+  const int t = g / nz;
+  iy = t % ny;
+  ix = t / ny;
+}
+
+PAL_SRP_HD double srp_distance(double x, double y, double z, double mx, double my, double mz) {
+  const double dx = x - mx, dy = y - my, dz = z - mz;
+  double q = dx * dx;
+  q = q + dy * dy;
+  q = q + dz * dz;
+  return srp_sqrt(q);
+}
+
+// r = rint(((dj - di) * fs) / c), half to even, as a double.  inv_c = 1 / c: the product a * inv_c lies within 2^-50 |a / c| of the
+// quotient, so wherever it is farther than kSrpNearHalf from a half-integer both round to the same integer (|a / c| < 2^26: a lag
+// beyond that is clipped by either); only a product that close to a half-integer pays for the division.
+constexpr double kSrpNearHalf = 1e-6;
+PAL_SRP_HD double srp_lag(double di, double dj, double fs, double c, double inv_c) {
+  const double a = (dj - di) * fs;
+  const double t = a * inv_c;
+  const double r = rint(t);
+  if (fabs(t) < 67108864.0 && !(fabs(fabs(t - r) - 0.5) < kSrpNearHalf)) return r;
+  return rint(srp_div(a, c));
+}
+
+// a term is clipped iff not |r| <= T, decided on the double (NaN and infinities are clipped)
+PAL_SRP_HD bool srp_clipped(double r, int T) { return !(fabs(r) <= double(T)); }
+
+// raw[u] = row[(-u) mod n] for |u| < n: the row has zero lag at index 0 and peaks at d_i - d_j; u counts d_j - d_i
+PAL_SRP_HD int srp_row_index(int u, int n) { return u > 0 ? n - u : -u; }
+
+// out[T + s] of a strip: sum over u = -W .. W of (W + 1 - |u|) * raw[s + u] in increasing u; the first product starts the sum
+PAL_SRP_HD double srp_smooth(const double* row, int n, int s, int W) {
+  double acc = double(1) * row[srp_row_index(s - W, n)];
+  for (int u = -W + 1; u <= W; ++u) acc = acc + double(W + 1 - (u < 0 ? -u : u)) * row[srp_row_index(s + u, n)];
+  return acc;
+}
+
+// cell g = (ix, iy, iz) of a map power[nx][ny][nz] is a peak iff it is not NaN and no cell of its (2R+1)^3 neighbourhood, cut at the
+// grid's border, is higher, or equal with a lower linear index
+PAL_SRP_HD bool srp_is_peak(const double* power, int nx, int ny, int nz, int ix, int iy, int iz, int R) {
+  const int g = (ix * ny + iy) * nz + iz;
+  const double v = power[g];
+  if (!(v == v)) return false;
+  const int x0 = ix - R < 0 ? 0 : ix - R, x1 = ix + R > nx - 1 ? nx - 1 : ix + R;
+  const int y0 = iy - R < 0 ? 0 : iy - R, y1 = iy + R > ny - 1 ? ny - 1 : iy + R;
+  const int z0 = iz - R < 0 ? 0 : iz - R, z1 = iz + R > nz - 1 ? nz - 1 : iz + R;
+  for (int x = x0; x <= x1; ++x)
+    for (int y = y0; y <= y1; ++y) {
+      const int base = (x * ny + y) * nz;
+      for (int z = z0; z <= z1; ++z) {
+        const double o = power[base + z];
+        if (o > v || (o == v && base + z < g)) return false;
+      }
+    }
+  return true;
+}
+
+// the order of the peaks: power descending, then index ascending.  true iff (pa, ga) comes before (pb, gb)
+PAL_SRP_HD bool srp_before(double pa, int ga, double pb, int gb) { return pa > pb || (pa == pb && ga < gb); }
+
+}  // namespace pal

@@ -346,6 +346,119 @@ class Engine:
         self._check(self._lib.pal_tdoa_consensus_dev(self._h, dev[0], dev[1], dev[2], int(b), int(m), int(k), ln.ctypes.data, int(tol),
                                                      int(rounds), dev[3], dev[4], dev[5]))
 
+    # ---- steered-response power map (specification: srp.py) ---------------------------------------
+    def gcc_phat_all_pairs_strips(self, frames, fs, T: int, W: int = 0, threshold_method="median", threshold_multiplier=1.0,
+                                  max_expected_delay=None, want_table=True):
+        """frames[B][M][L] (or [M][L]) -> (strips[B][P][2T+1], table[B][P] or None): every pair's GCC-PHAT row around zero lag in the
+        centred lag s = d_j - d_i (``strips[..][p][T + s]``), smoothed by a triangle of half-width ``W`` (0..32; 0: the samples
+        themselves), and the ordinary one-peak table of the same rows - see srp.strips.  T >= 0, T + W <= L - 1."""
+        x = f64(frames)
+        squeeze = x.ndim == 2
+        if squeeze:
+            x = x[None]
+        if x.ndim != 3:
+            raise ValueError("frames must be [M][L] or [B][M][L]")
+        b, m, length = x.shape
+        npairs = m * (m - 1) // 2
+        t, w = int(T), int(W)
+        out = np.zeros((b, npairs, max(2 * t + 1, 1)), dtype=np.float64)
+        table = np.zeros((b, npairs), dtype=RECORD) if want_table else None
+        prm = make_params(fs, 1, threshold_method, threshold_multiplier, max_expected_delay)
+        self._check(self._lib.pal_gcc_phat_all_pairs_strips(self._h, x.ctypes.data, b, m, length, C.byref(prm), t, w, ptr(table),
+                                                            out.ctypes.data))
+        if squeeze:
+            out, table = out[0], None if table is None else table[0]
+        return out, table
+
+    def gcc_phat_all_pairs_strips_dev(self, d_frames: int, b: int, m: int, length: int, prm: PhatParams, T: int, W: int, d_strips: int,
+                                      d_table: int = 0) -> None:
+        """Asynchronous: frames[b][m][length], strips[b][P][2T+1] and the table (0 = not wanted) stay in HBM."""
+        self._check(self._lib.pal_gcc_phat_all_pairs_strips_dev(self._h, C.c_void_p(d_frames), int(b), int(m), int(length), C.byref(prm),
+                                                                int(T), int(W), C.c_void_p(d_table) if d_table else None,
+                                                                C.c_void_p(d_strips)))
+
+    @staticmethod
+    def _srp_grid(lo, hi, count) -> _ffi.SrpGrid:
+        lo, hi = np.asarray(lo, dtype=np.float64).reshape(-1), np.asarray(hi, dtype=np.float64).reshape(-1)
+        count = np.asarray(count, dtype=np.int64).reshape(-1)
+        if lo.shape != (3,) or hi.shape != (3,) or count.shape != (3,):
+            raise ValueError("lo, hi and count have three entries each")
+        if np.any(np.abs(count) >= 2 ** 31):
+            raise ValueError("a cell count does not fit int32")
+        g = _ffi.SrpGrid()
+        for a in range(3):
+            g.lo[a], g.hi[a], g.count[a] = float(lo[a]), float(hi[a]), int(count[a])
+        g.reserved = 0
+        return g
+
+    def srp_map(self, strips, mic_positions, fs, c, lo, hi, count, pair_weights=None, K: int = 0, R: int = 1,
+                outputs=("power", "peaks", "summary")):
+        """strips[B][P][2T+1] (or [P][2T+1]) -> (power[B][G], peaks[B][K] of _ffi.SRP_PEAK, summary[B] of _ffi.SRP_FRAME): the steered-
+        response power of every cell of the grid ``count`` cells over the box ``lo .. hi`` (g = (ix * ny + iy) * nz + iz), optionally
+        weighted per pair, the first ``K`` (0..8) peaks of each map within the neighbourhood radius ``R`` (1..4 cells) and the clipped
+        terms - see srp.srp_map and srp.map_peaks.  ``outputs``: the names to compute; the others (and ``peaks`` when K = 0) are None."""
+        st = f64(strips)
+        if st.ndim == 2:
+            st = st[None]
+        if st.ndim != 3 or st.shape[2] % 2 != 1:
+            raise ValueError("strips must be [P][2T+1] or [B][P][2T+1]")
+        mics = f64(mic_positions)
+        if mics.ndim != 2 or mics.shape[1] != 3:
+            raise ValueError("mic_positions must be [M][3]")
+        b, p, width = st.shape
+        m = mics.shape[0]
+        if m >= 2 and p != m * (m - 1) // 2:
+            raise ValueError(f"strips of {m} microphones have {m * (m - 1) // 2} rows per frame, got {p}")
+        wt = None if pair_weights is None else f64(pair_weights).reshape(b, p)
+        grid = self._srp_grid(lo, hi, count)
+        k = int(K)
+        if any(name not in ("power", "peaks", "summary") for name in outputs):
+            raise ValueError("outputs: 'power', 'peaks', 'summary'")
+        cells = max(int(grid.count[0]), 0) * max(int(grid.count[1]), 0) * max(int(grid.count[2]), 0)
+        big = not all(1 <= int(grid.count[a]) <= 1024 for a in range(3)) or cells > (1 << 24)      # the call refuses it
+        power = np.zeros((b, 1 if big else cells), dtype=np.float64) if "power" in outputs else None
+        peaks = np.zeros((b, k), dtype=_ffi.SRP_PEAK) if "peaks" in outputs and 0 < k <= _ffi.SRP_MAX_PEAKS else None
+        summ = np.zeros(b, dtype=_ffi.SRP_FRAME) if "summary" in outputs else None
+        self._check(self._lib.pal_srp_map(self._h, st.ctypes.data, b, m, (width - 1) // 2, mics.ctypes.data, float(fs), float(c),
+                                          C.byref(grid), ptr(wt), k, int(R), ptr(power), ptr(peaks), ptr(summ)))
+        return power, peaks, summ
+
+    def srp_map_dev(self, d_strips: int, b: int, T: int, mic_positions, fs, c, lo, hi, count, d_pair_weights: int = 0, K: int = 0, R: int = 1,
+                    d_power: int = 0, d_peaks: int = 0, d_summary: int = 0) -> None:
+        """Asynchronous: strips[b][P][2T+1], the optional pair_weights[b][P] and the requested outputs (0 = not wanted; at least one)
+        stay in HBM; ``mic_positions`` and the grid are read before the call returns."""
+        mics = f64(mic_positions)
+        if mics.ndim != 2 or mics.shape[1] != 3:
+            raise ValueError("mic_positions must be [M][3]")
+        grid = self._srp_grid(lo, hi, count)
+        dev = [C.c_void_p(int(d)) if d else None for d in (d_strips, d_pair_weights, d_power, d_peaks, d_summary)]
+        self._check(self._lib.pal_srp_map_dev(self._h, dev[0], int(b), mics.shape[0], int(T), mics.ctypes.data, float(fs), float(c),
+                                              C.byref(grid), dev[1], int(K), int(R), dev[2], dev[3], dev[4]))
+
+    def srp_peaks(self, power, lo, hi, count, K: int = 1, R: int = 1):
+        """power[B][nx][ny][nz] (or [nx][ny][nz], or [B][G]) -> (peaks[B][K] of _ffi.SRP_PEAK, summary[B] of _ffi.SRP_FRAME): the first
+        ``K`` peaks of every map by the neighbourhood rule of radius ``R`` - see srp.map_peaks."""
+        grid = self._srp_grid(lo, hi, count)
+        cells = int(grid.count[0]) * int(grid.count[1]) * int(grid.count[2])
+        pw = f64(power)
+        ok = all(1 <= int(grid.count[a]) <= 1024 for a in range(3)) and cells <= (1 << 24)          # otherwise the call refuses the grid
+        if ok:
+            if pw.size % cells:
+                raise ValueError("power does not hold whole maps of the grid")
+            pw = pw.reshape(-1, cells)
+        b = pw.shape[0] if ok else 1
+        k = int(K)
+        peaks = np.zeros((b, k if 0 < k <= _ffi.SRP_MAX_PEAKS else 1), dtype=_ffi.SRP_PEAK)
+        summ = np.zeros(b, dtype=_ffi.SRP_FRAME)
+        self._check(self._lib.pal_srp_peaks(self._h, pw.ctypes.data, b, C.byref(grid), k, int(R), peaks.ctypes.data, summ.ctypes.data))
+        return peaks, summ
+
+    def srp_peaks_dev(self, d_power: int, b: int, lo, hi, count, K: int, R: int, d_peaks: int, d_summary: int = 0) -> None:
+        """Asynchronous: power[b][G], peaks[b][K] and the summary (0 = not wanted) stay in HBM."""
+        grid = self._srp_grid(lo, hi, count)
+        self._check(self._lib.pal_srp_peaks_dev(self._h, C.c_void_p(d_power) if d_power else None, int(b), C.byref(grid), int(K), int(R),
+                                                C.c_void_p(d_peaks) if d_peaks else None, C.c_void_p(d_summary) if d_summary else None))
+
     def solve_positions(self, tables, lengths, mic_positions, fs, c, calib_delays=None, weights="ones", buffer=5.0, grid=solve.GRID,
                         max_iter=solve.MAX_ITER, extra_starts=None, loss="linear", f_scale=1.0, return_pair_weights=False,
                         closure_tol=1, closure_min_votes=1, closure_mode="soft"):

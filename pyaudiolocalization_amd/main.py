@@ -201,6 +201,40 @@ def solve_positions_device(tables, lengths, mic_positions, fs, c, calib_delays=N
     return (pos, rec) if return_records else pos
 
 
+def srp_positions_device(frames, mic_positions, fs, c, lo, hi, count, W=8, K=1, R=1, refine=False, T=None, pair_weights=None, engine=None,
+                         threshold_method="median", threshold_multiplier=1.0, max_expected_delay=None, **solve_args):
+    """frames[B][M][L] (or [M][L]) -> peaks[B][K] of _ffi.SRP_PEAK: the first ``K`` maxima (neighbourhood radius ``R`` cells) of every
+    frame's steered-response power map over the grid of ``count`` cells in the box ``lo .. hi`` (Engine.gcc_phat_all_pairs_strips with
+    smoothing ``W``, then Engine.srp_map; rules: srp.py).  ``T``: the strips' half-width, by default srp.half_width, for which no lag
+    is clipped.  The map reads the rows at the true delay, so the table's index mapping plays no part, and a second source shows as a
+    second peak.  ``refine=True`` -> (peaks, records of solve.POSITION): every frame's first peak goes to Engine.solve_positions as one
+    more start (``extra_starts``), on the one-peak table of the same rows with ``consensus.centred`` applied to ``k_sel`` (the
+    precondition solve_positions_device documents); the solve's winner rule is unchanged, ``solve_args`` go to it."""
+    from . import consensus, srp
+    eng = engine or default_engine()
+    x = np.ascontiguousarray(frames, dtype=np.float64)
+    one = x.ndim == 2
+    if one:
+        x = x[None]
+    if x.ndim != 3:
+        raise ValueError("frames must be [M][L] or [B][M][L]")
+    mics = np.ascontiguousarray(mic_positions, dtype=np.float64)
+    length = x.shape[2]
+    half = srp.half_width(mics, fs, c) if T is None else int(T)
+    strips, table = eng.gcc_phat_all_pairs_strips(x, fs, half, W, threshold_method, threshold_multiplier, max_expected_delay,
+                                                  want_table=bool(refine))
+    peaks = eng.srp_map(strips, mics, fs, c, lo, hi, count, pair_weights, K, R, outputs=("peaks",))[1]
+    if not refine:
+        return peaks[0] if one else peaks
+    tab = table.copy()
+    tab["k_sel"] = consensus.centred(tab["k_sel"], length)
+    first = peaks[:, 0]
+    centre = 0.5 * (np.asarray(lo, dtype=np.float64) + np.asarray(hi, dtype=np.float64))
+    starts = np.where((first["index"] >= 0)[:, None], np.stack([first["x"], first["y"], first["z"]], axis=1), centre[None, :])
+    rec = eng.solve_positions(tab, length, mics, fs, c, extra_starts=starts[:, None, :], **solve_args)
+    return (peaks[0], rec[0]) if one else (peaks, rec)
+
+
 def localize_sound_source(config, calibration_data=None, audio_files=None, use_simulation=True, show_plots=True):
     fs = config["fs"]
     duration = config["duration"]

@@ -329,11 +329,28 @@ int pal_tdoa_consensus(pal_handle h, const pal_pair_record* tables, const int32_
  *   the first K are written, absent entries as index -1 and all else 0.  summary (may be NULL): n_peaks = entries present, clipped = 0.
  *   1 <= K <= PAL_SRP_MAX_PEAKS, 1 <= R <= PAL_SRP_MAX_RADIUS.
  *
+ * pal_srp_zoom*: strips[B][P][2T+1], seeds[B][K] (pal_srp_peak, as pal_srp_map writes them) -> out[B][K]: a coarse-to-fine search
+ *   around every seed with a continuous rule (srp.zoom).  A level has a centre and a half-extent per axis; its Z^3 points are the cell
+ *   centres of the box centre -+ half-extent, by the map's own point and index arithmetic.  Level 0: the seed's (x, y, z) and half0[3]
+ *   (metres).  The power of a point sums, over the pairs in the order of the map kernel's microphone tiles (srp.tile_order),
+ *     w_p * (s0 + f * (s1 - s0)),   q = ((d_j - d_i) * fs) / c,  k = floor(q),  f = q - k,  s0 = strips[p][T + k],  s1 = strips[p][T + k + 1]
+ *   every product rounded; a term with k < -T or k > T - 1 (or q not finite) is clipped: it adds nothing and is counted.  The best cell
+ *   of a level is the first by (power descending, index ascending) among the cells that are not NaN; the next level has its centre and
+ *   the half-extent (hi - lo) / Z, one cell.  Where every cell of a level is NaN the zoom stops: the record keeps the centre that level
+ *   started from, power = NaN and the levels completed before it.  A seed with index < 0 is absent: seed = -1 and all else 0.  The
+ *   order of every sum is fixed: the same input gives the same bytes whatever B and K are, and they are the specification's bytes.
+ *   mics[M][3] and half0[3] are host memory, read before the call returns.
+ *   2 <= Z <= PAL_SRP_MAX_ZOOM_CELLS, 1 <= levels <= PAL_SRP_MAX_ZOOM_LEVELS, 1 <= K <= PAL_SRP_MAX_PEAKS, T >= 1, every half0[a]
+ *   finite and > 0, microphone coordinates finite, fs > 0, c > 0, M >= 2, B >= 1, no NULL buffer but d_pair_weights: PAL_ERR_INVALID
+ *   otherwise; M > 4096: PAL_ERR_UNSUPPORTED.
+ *
  * The _dev forms are asynchronous on the engine's stream (results complete after pal_synchronize); every `d_` pointer comes from
  * pal_device_alloc.  Every argument check is made before any buffer is touched. */
 #define PAL_SRP_MAX_SMOOTH 32
 #define PAL_SRP_MAX_PEAKS 8
 #define PAL_SRP_MAX_RADIUS 4
+#define PAL_SRP_MAX_ZOOM_CELLS 16
+#define PAL_SRP_MAX_ZOOM_LEVELS 16
 typedef struct pal_srp_grid {    /* 64 bytes */
   double lo[3], hi[3];    /* the box                                                               */
   int32_t count[3];       /* cells per axis                                                        */
@@ -350,6 +367,13 @@ typedef struct pal_srp_frame {   /* 16 bytes */
   int32_t n_peaks;        /* entries present in the frame's peaks                                  */
   int32_t reserved;
 } pal_srp_frame;
+typedef struct pal_srp_zoom_record {   /* 48 bytes: one (frame, seed) of pal_srp_zoom (a typedef and a function cannot share a name in C) */
+  double x, y, z;         /* the best cell's centre at the last completed level                    */
+  double power;           /* the power of that cell; NaN where a level had no cell that is not NaN */
+  int64_t clipped;        /* terms clipped over all cells of all levels run                        */
+  int32_t seed;           /* the seed record's index, -1 = absent (then all else 0)                */
+  int32_t levels;         /* levels completed                                                      */
+} pal_srp_zoom_record;
 int pal_gcc_phat_all_pairs_strips_dev(pal_handle h, const double* d_frames, int B, int M, int L, const pal_phat_params* prm, int T, int W,
                                       pal_pair_record* d_table, double* d_strips);
 int pal_gcc_phat_all_pairs_strips(pal_handle h, const double* frames, int B, int M, int L, const pal_phat_params* prm, int T, int W,
@@ -363,6 +387,12 @@ int pal_srp_peaks_dev(pal_handle h, const double* d_power, int B, const pal_srp_
                       pal_srp_frame* d_summary);
 int pal_srp_peaks(pal_handle h, const double* power, int B, const pal_srp_grid* grid, int K, int R, pal_srp_peak* peaks,
                   pal_srp_frame* summary);
+int pal_srp_zoom_dev(pal_handle h, const double* d_strips, int B, int M, int T, const double* mics, double fs, double c,
+                     const double* d_pair_weights, const pal_srp_peak* d_seeds, int K, const double* half0, int Z, int levels,
+                     pal_srp_zoom_record* d_out);
+int pal_srp_zoom(pal_handle h, const double* strips, int B, int M, int T, const double* mics, double fs, double c,
+                 const double* pair_weights, const pal_srp_peak* seeds, int K, const double* half0, int Z, int levels,
+                 pal_srp_zoom_record* out);
 
 /* single-pair signatures: phat_correlation(sig1, sig2) (utils.py:108) -> corr[n1+n2-1] */
 int pal_phat_correlation(pal_handle h, const double* sig1, int n1, const double* sig2, int n2, double* corr);

@@ -42,6 +42,10 @@ SRP_PEAK = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("power", "<f8"),
 SRP_FRAME = np.dtype([("clipped", "<i8"), ("n_peaks", "<i4"), ("reserved", "<i4")])
 assert SRP_PEAK.itemsize == 40 and SRP_FRAME.itemsize == 16
 SRP_MAX_SMOOTH, SRP_MAX_PEAKS, SRP_MAX_RADIUS = 32, 8, 4
+# pal_srp_zoom_record (48 bytes)
+SRP_ZOOM = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("power", "<f8"), ("clipped", "<i8"), ("seed", "<i4"), ("levels", "<i4")])
+assert SRP_ZOOM.itemsize == 48
+SRP_MAX_ZOOM_CELLS, SRP_MAX_ZOOM_LEVELS = 16, 16
 
 # one row of the TDOA table (pal_pair_record, 48 bytes)
 RECORD = np.dtype([("k_sel", "<i4"), ("branch", "<i4"), ("k_argmax", "<i4"), ("n_sel", "<i4"),
@@ -119,6 +123,10 @@ SIGNATURES = {
                               C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pal_srp_peaks_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(SrpGrid), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pal_srp_peaks": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(SrpGrid), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pal_srp_zoom_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "pal_srp_zoom": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                               C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "pal_phat_correlation": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "pal_get_time_delays_phat": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(PhatParams), C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

@@ -258,6 +258,10 @@ struct Engine {
                   const double* d_pair_weights, int K, int R, double* d_power, pal_srp_peak* d_peaks, pal_srp_frame* d_summary);
   int srp_peaks_check(int B, const pal_srp_grid* grid, int K, int R);
   int srp_peaks_dev(const double* d_power, int B, const pal_srp_grid* grid, int K, int R, pal_srp_peak* d_peaks, pal_srp_frame* d_summary);
+  // the coarse-to-fine zoom around seeds[B][K] (k_srp_zoom): `mics` and `half0` are host memory
+  int srp_zoom_check(int B, int M, int T, const double* mics, double fs, double c, int K, const double* half0, int Z, int levels);
+  int srp_zoom_dev(const double* d_strips, int B, int M, int T, const double* mics, double fs, double c, const double* d_pair_weights,
+                   const pal_srp_peak* d_seeds, int K, const double* half0, int Z, int levels, pal_srp_zoom_record* d_out);
   int32_t* solve_idx = nullptr;    // device table pair -> i | j << 16 of the last microphone count
   int solve_idx_M = 0;
   // resample.hip: the right wing of the interpolation filter as pal_resample_set_filter received it, and the ratio whose scaled

@@ -833,6 +833,37 @@ int pal_srp_peaks(pal_handle h, const double* power, int B, const pal_srp_grid* 
   return pal_synchronize(h);
 }
 
+int pal_srp_zoom_dev(pal_handle h, const double* d_strips, int B, int M, int T, const double* mics, double fs, double c,
+                     const double* d_pair_weights, const pal_srp_peak* d_seeds, int K, const double* half0, int Z, int levels,
+                     pal_srp_zoom_record* d_out) {
+  ENGINE(h);
+  return e->srp_zoom_dev(d_strips, B, M, T, mics, fs, c, d_pair_weights, d_seeds, K, half0, Z, levels, d_out);
+}
+
+int pal_srp_zoom(pal_handle h, const double* strips, int B, int M, int T, const double* mics, double fs, double c,
+                 const double* pair_weights, const pal_srp_peak* seeds, int K, const double* half0, int Z, int levels,
+                 pal_srp_zoom_record* out) {
+  ENGINE(h);
+  PAL_TRY(e->srp_zoom_check(B, M, T, mics, fs, c, K, half0, Z, levels));
+  if (!strips || !seeds || !out) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  const size_t P = size_t(M) * size_t(M - 1) / 2, np = size_t(B) * P, nk = size_t(B) * size_t(K);
+  // staged inputs [strips | pair_weights | seeds] and the output records, one block each
+  Carve ci;
+  const size_t sbytes = np * size_t(2 * T + 1) * sizeof(double);
+  const size_t o_st = ci.take(sbytes), o_w = ci.take(pair_weights ? np * sizeof(double) : 0), o_sd = ci.take(nk * sizeof(pal_srp_peak));
+  char *in = nullptr, *dout = nullptr;
+  PAL_TRY(e->scratch(kWsStageIn, ci.off, &in));
+  PAL_TRY(e->scratch(kWsStageOut, nk * sizeof(pal_srp_zoom_record), &dout));
+  PAL_TRY(e->check(hipMemcpyAsync(in + o_st, strips, sbytes, hipMemcpyHostToDevice, e->stream), "strips upload"));
+  if (pair_weights) PAL_TRY(e->check(hipMemcpyAsync(in + o_w, pair_weights, np * sizeof(double), hipMemcpyHostToDevice, e->stream), "weights upload"));
+  PAL_TRY(e->check(hipMemcpyAsync(in + o_sd, seeds, nk * sizeof(pal_srp_peak), hipMemcpyHostToDevice, e->stream), "seeds upload"));
+  PAL_TRY(e->srp_zoom_dev(reinterpret_cast<const double*>(in + o_st), B, M, T, mics, fs, c,
+                          pair_weights ? reinterpret_cast<const double*>(in + o_w) : nullptr, reinterpret_cast<const pal_srp_peak*>(in + o_sd), K,
+                          half0, Z, levels, reinterpret_cast<pal_srp_zoom_record*>(dout)));
+  PAL_TRY(e->check(hipMemcpyAsync(out, dout, nk * sizeof(pal_srp_zoom_record), hipMemcpyDeviceToHost, e->stream), "zoom download"));
+  return pal_synchronize(h);
+}
+
 static int single_pair(Engine* e, const double* sig1, int n1, const double* sig2, int n2, const pal_phat_params* prm,
                        int32_t* k_out, pal_pair_record* rec, double* corr) {
   if (!sig1 || !sig2) return e->fail(PAL_ERR_INVALID, "NULL signal");

@@ -459,6 +459,50 @@ class Engine:
         self._check(self._lib.pal_srp_peaks_dev(self._h, C.c_void_p(d_power) if d_power else None, int(b), C.byref(grid), int(K), int(R),
                                                 C.c_void_p(d_peaks) if d_peaks else None, C.c_void_p(d_summary) if d_summary else None))
 
+    def srp_zoom(self, strips, mic_positions, fs, c, seeds, half0, Z: int = 8, levels: int = 3, pair_weights=None):
+        """strips[B][P][2T+1] (or [P][2T+1]) and seeds[B][K] (or [K]) of _ffi.SRP_PEAK, as srp_map returns its peaks -> out[B][K] of
+        _ffi.SRP_ZOOM: a coarse-to-fine search around every seed, ``levels`` levels of ``Z``^3 cells, the first over the seed's position
+        -+ ``half0[3]`` metres, each next one over the best cell and half of each neighbour, with the strip read at the fractional lag
+        (linear interpolation) - see srp.zoom, which it equals byte for byte.  An absent seed (index -1) gives an absent record."""
+        st = f64(strips)
+        if st.ndim == 2:
+            st = st[None]
+        if st.ndim != 3 or st.shape[2] % 2 != 1:
+            raise ValueError("strips must be [P][2T+1] or [B][P][2T+1]")
+        mics = f64(mic_positions)
+        if mics.ndim != 2 or mics.shape[1] != 3:
+            raise ValueError("mic_positions must be [M][3]")
+        b, p, width = st.shape
+        m = mics.shape[0]
+        if m >= 2 and p != m * (m - 1) // 2:
+            raise ValueError(f"strips of {m} microphones have {m * (m - 1) // 2} rows per frame, got {p}")
+        sd = np.ascontiguousarray(seeds, dtype=_ffi.SRP_PEAK)
+        if sd.size % b:
+            raise ValueError("seeds must be [K] or [B][K]")
+        sd = sd.reshape(b, -1)
+        wt = None if pair_weights is None else f64(pair_weights).reshape(b, p)
+        h0 = f64(half0).reshape(-1)
+        if h0.shape != (3,):
+            raise ValueError("half0 has three entries")
+        out = np.zeros(sd.shape, dtype=_ffi.SRP_ZOOM)
+        self._check(self._lib.pal_srp_zoom(self._h, st.ctypes.data, b, m, (width - 1) // 2, mics.ctypes.data, float(fs), float(c), ptr(wt),
+                                           sd.ctypes.data, sd.shape[1], h0.ctypes.data, int(Z), int(levels), out.ctypes.data))
+        return out
+
+    def srp_zoom_dev(self, d_strips: int, b: int, T: int, mic_positions, fs, c, d_seeds: int, K: int, half0, Z: int, levels: int, d_out: int,
+                     d_pair_weights: int = 0) -> None:
+        """Asynchronous: strips[b][P][2T+1], seeds[b][K], the optional pair_weights[b][P] and out[b][K] stay in HBM; ``mic_positions``
+        and ``half0`` are read before the call returns."""
+        mics = f64(mic_positions)
+        if mics.ndim != 2 or mics.shape[1] != 3:
+            raise ValueError("mic_positions must be [M][3]")
+        h0 = f64(half0).reshape(-1)
+        if h0.shape != (3,):
+            raise ValueError("half0 has three entries")
+        dev = [C.c_void_p(int(d)) if d else None for d in (d_strips, d_pair_weights, d_seeds, d_out)]
+        self._check(self._lib.pal_srp_zoom_dev(self._h, dev[0], int(b), mics.shape[0], int(T), mics.ctypes.data, float(fs), float(c), dev[1],
+                                               dev[2], int(K), h0.ctypes.data, int(Z), int(levels), dev[3]))
+
     def solve_positions(self, tables, lengths, mic_positions, fs, c, calib_delays=None, weights="ones", buffer=5.0, grid=solve.GRID,
                         max_iter=solve.MAX_ITER, extra_starts=None, loss="linear", f_scale=1.0, return_pair_weights=False,
                         closure_tol=1, closure_min_votes=1, closure_mode="soft"):

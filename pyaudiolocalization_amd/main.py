@@ -202,14 +202,18 @@ def solve_positions_device(tables, lengths, mic_positions, fs, c, calib_delays=N
 
 
 def srp_positions_device(frames, mic_positions, fs, c, lo, hi, count, W=8, K=1, R=1, refine=False, T=None, pair_weights=None, engine=None,
-                         threshold_method="median", threshold_multiplier=1.0, max_expected_delay=None, **solve_args):
+                         threshold_method="median", threshold_multiplier=1.0, max_expected_delay=None, zoom=None, **solve_args):
     """frames[B][M][L] (or [M][L]) -> peaks[B][K] of _ffi.SRP_PEAK: the first ``K`` maxima (neighbourhood radius ``R`` cells) of every
     frame's steered-response power map over the grid of ``count`` cells in the box ``lo .. hi`` (Engine.gcc_phat_all_pairs_strips with
     smoothing ``W``, then Engine.srp_map; rules: srp.py).  ``T``: the strips' half-width, by default srp.half_width, for which no lag
     is clipped.  The map reads the rows at the true delay, so the table's index mapping plays no part, and a second source shows as a
     second peak.  ``refine=True`` -> (peaks, records of solve.POSITION): every frame's first peak goes to Engine.solve_positions as one
     more start (``extra_starts``), on the one-peak table of the same rows with ``consensus.centred`` applied to ``k_sel`` (the
-    precondition solve_positions_device documents); the solve's winner rule is unchanged, ``solve_args`` go to it."""
+    precondition solve_positions_device documents); the solve's winner rule is unchanged, ``solve_args`` go to it.
+    ``zoom=(Z, levels)`` or ``(Z, levels, span)``: Engine.srp_zoom refines the K peaks on the same strips, the first level over each
+    peak -+ ``span`` (default 1.0) cells of the map -> (peaks, zoomed[B][K] of _ffi.SRP_ZOOM), with ``refine=True`` -> (peaks, zoomed,
+    records) and the zoomed position, where present, as the solve's start.  The zoom is a local search: it finds the maximum of the
+    interpolated power that the first box holds."""
     from . import consensus, srp
     eng = engine or default_engine()
     x = np.ascontiguousarray(frames, dtype=np.float64)
@@ -224,14 +228,28 @@ def srp_positions_device(frames, mic_positions, fs, c, lo, hi, count, W=8, K=1, 
     strips, table = eng.gcc_phat_all_pairs_strips(x, fs, half, W, threshold_method, threshold_multiplier, max_expected_delay,
                                                   want_table=bool(refine))
     peaks = eng.srp_map(strips, mics, fs, c, lo, hi, count, pair_weights, K, R, outputs=("peaks",))[1]
+    zoomed = None
+    if zoom is not None:
+        if len(zoom) not in (2, 3):
+            raise ValueError("zoom is (Z, levels) or (Z, levels, span)")
+        span = float(zoom[2]) if len(zoom) == 3 else 1.0
+        lo_, hi_, count_ = srp.check_grid(lo, hi, count)
+        zoomed = eng.srp_zoom(strips, mics, fs, c, peaks, span * ((hi_ - lo_) / count_), int(zoom[0]), int(zoom[1]), pair_weights)
     if not refine:
-        return peaks[0] if one else peaks
+        if zoomed is None:
+            return peaks[0] if one else peaks
+        return (peaks[0], zoomed[0]) if one else (peaks, zoomed)
     tab = table.copy()
     tab["k_sel"] = consensus.centred(tab["k_sel"], length)
     first = peaks[:, 0]
     centre = 0.5 * (np.asarray(lo, dtype=np.float64) + np.asarray(hi, dtype=np.float64))
     starts = np.where((first["index"] >= 0)[:, None], np.stack([first["x"], first["y"], first["z"]], axis=1), centre[None, :])
+    if zoomed is not None:
+        zf = zoomed[:, 0]
+        starts = np.where(((zf["seed"] >= 0) & (zf["levels"] > 0))[:, None], np.stack([zf["x"], zf["y"], zf["z"]], axis=1), starts)
     rec = eng.solve_positions(tab, length, mics, fs, c, extra_starts=starts[:, None, :], **solve_args)
+    if zoomed is not None:
+        return (peaks[0], zoomed[0], rec[0]) if one else (peaks, zoomed, rec)
     return (peaks[0], rec[0]) if one else (peaks, rec)
 
 

@@ -1,5 +1,5 @@
 """Steered-response power (SRP-PHAT) map: the device rule (csrc/srp.hip, csrc/srp_math.h, pal_gcc_phat_all_pairs_strips*, pal_srp_map*,
-pal_srp_peaks*) in NumPy.
+pal_srp_peaks*, pal_srp_zoom*) in NumPy.
 
 For every candidate position the map sums, over all microphone pairs, the pair's GCC-PHAT row at the lag that position predicts.  It
 uses the whole row and picks no peak per pair, so a wrong first peak of some pairs costs a little power and nothing else, the table's
@@ -17,7 +17,10 @@ index mapping plays no part, and several sources show as several maxima.  Conven
   contributes nothing and is counted;
 - a cell is a **peak** iff no cell of its (2R+1)^3 neighbourhood, cut at the grid's border, is higher, and among equal cells of that
   neighbourhood it has the lowest linear index; a NaN cell is no peak and hides none.  Peaks are ordered by power descending, then by
-  index.
+  index;
+- the map is piecewise constant in space (``rint`` picks one sample), so below about c / fs a finer grid finds plateaus.  The **zoom**
+  (``zoom``) refines a peak with a continuous rule instead: the strip read at the fractional lag with linear interpolation, over small
+  boxes that shrink around the best cell, the terms added in the fixed order ``tile_order``.
 
 Every product is rounded before it is added (no fused multiply-add), square root and division are correctly rounded and rint rounds
 half to even, so the device's grid points, lags, clip decisions, smoothing sums and peak marks equal these bit for bit.  The order of
@@ -32,7 +35,10 @@ from ._ffi import SRP_FRAME as FRAME                                   # pal_srp
 from ._ffi import SRP_MAX_PEAKS as MAX_PEAKS
 from ._ffi import SRP_MAX_RADIUS as MAX_RADIUS
 from ._ffi import SRP_MAX_SMOOTH as MAX_SMOOTH
+from ._ffi import SRP_MAX_ZOOM_CELLS as MAX_ZOOM_CELLS
+from ._ffi import SRP_MAX_ZOOM_LEVELS as MAX_ZOOM_LEVELS
 from ._ffi import SRP_PEAK as PEAK                                      # pal_srp_peak
+from ._ffi import SRP_ZOOM as ZOOM                                      # pal_srp_zoom_record
 
 MAX_COUNT = 1024                                                        # cells per axis
 MAX_CELLS = 1 << 24
@@ -169,6 +175,134 @@ def srp_map(strips_, T: int, mics, fs, c, lo, hi, count, pair_weights=None, retu
         power[g0:g0 + chunk] = acc
         total[g0:g0 + chunk] = np.sum(np.abs(v), axis=1)
     return (power, clipped, total) if return_abs else (power, clipped)
+
+
+def tile_order(M: int) -> np.ndarray:
+    """The pair indices (row-major over i < j) in the order k_srp_map and k_srp_zoom add their terms: microphone tiles of 16, the loops
+    nested (ti, tj >= ti, i in tile ti, j in tile tj, j > i).  For M <= 16 it is pair order."""
+    M = int(M)
+    if M < 2:
+        raise ValueError("M >= 2")
+    tiles = (M + 15) // 16
+    out = []
+    for ti in range(tiles):
+        for tj in range(ti, tiles):
+            for i in range(16 * ti, min(16 * ti + 16, M - 1)):
+                row0 = i * M - i * (i + 1) // 2 - i - 1
+                out.extend(row0 + j for j in range(max(16 * tj, i + 1), min(16 * tj + 16, M)))
+    return np.asarray(out, dtype=np.int64)
+
+
+def zoom_terms(strips_, T: int, points, mics, fs, c, pair_weights=None):
+    """The zoom's terms of every point: (v[G][P] with 0 where clipped, out[G][P] bool: clipped, q, k, f [G][P]).  For pair p = (i, j):
+    ``q = ((d_j - d_i) * fs) / c``, ``k = floor(q)``, ``f = q - k``; clipped iff not (k >= -T and k <= T - 1), decided on the doubles;
+    otherwise ``v = s0 + f * (s1 - s0)`` with ``s0 = strips[p][T + k]``, ``s1 = strips[p][T + k + 1]`` (the product rounded before the
+    addition), then ``v = w_p * v``."""
+    st = np.asarray(strips_, dtype=np.float64)
+    T = int(T)
+    q = lag_quotients(points, mics, fs, c)
+    with np.errstate(invalid="ignore"):
+        k = np.floor(q)
+        f = q - k
+        out = ~((k >= -T) & (k <= T - 1))
+    at = np.where(out, 0, k).astype(np.int64) + T
+    rows = np.arange(st.shape[0])[None, :]
+    s0, s1 = st[rows, at], st[rows, at + 1]                                                      # at <= 2T - 1: T >= 1
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = s0 + np.where(out, 0.0, f) * (s1 - s0)
+        if pair_weights is not None:
+            v = np.asarray(pair_weights, dtype=np.float64).reshape(1, -1) * v
+    return np.where(out, 0.0, v), out, q, k, f
+
+
+def zoom_box(ctr, half):
+    """-> (lo[3], hi[3]) of a level: ctr - half, ctr + half."""
+    ctr, half = np.asarray(ctr, dtype=np.float64), np.asarray(half, dtype=np.float64)
+    return ctr - half, ctr + half
+
+
+def zoom_next_half(lo, hi, Z: int) -> np.ndarray:
+    """The next level's half-extent: one cell of this level, (hi - lo) / Z."""
+    return (np.asarray(hi, dtype=np.float64) - np.asarray(lo, dtype=np.float64)) / np.float64(int(Z))
+
+
+def zoom_level(strips_, T: int, mics, fs, c, ctr, half, Z: int, pair_weights=None, order=None):
+    """One level -> (power[Z^3], clipped, best index or -1, points[Z^3][3]).  The terms are added in ``tile_order``; the best cell is the
+    first by (power descending, index ascending) among the cells that are not NaN."""
+    lo, hi = zoom_box(ctr, half)
+    with np.errstate(invalid="ignore", over="ignore"):
+        step = [(hi[a] - lo[a]) / np.float64(Z) for a in range(3)]
+        axes = [lo[a] + (np.arange(Z, dtype=np.float64) + 0.5) * step[a] for a in range(3)]
+    # grid_points' arithmetic without its checks: after many levels a box collapses to a point (hi == lo), and that is still a level
+    x, y, z = np.meshgrid(*axes, indexing="ij")
+    pts = np.ascontiguousarray(np.stack([x.reshape(-1), y.reshape(-1), z.reshape(-1)], axis=1))
+    with np.errstate(invalid="ignore", over="ignore"):
+        v, out, _, _, _ = zoom_terms(strips_, T, pts, mics, fs, c, pair_weights)
+        acc = np.zeros(pts.shape[0])
+        for p in (tile_order(np.asarray(mics).shape[0]) if order is None else order):
+            acc = acc + v[:, p]                            # v is 0.0 where clipped, and acc is never -0.0: adding it adds nothing
+    ok = ~np.isnan(acc)
+    best = -1
+    if np.any(ok):
+        best = int(np.flatnonzero(ok & (acc == np.max(acc[ok])))[0])
+    return acc, int(np.count_nonzero(out)), best, pts
+
+
+def zoom(strips_, T: int, mics, fs, c, seeds, half0, Z: int = 8, levels: int = 3, pair_weights=None, return_levels=False):
+    """strips[P][2T + 1] of one frame and seeds[K] of PEAK -> out[K] of ZOOM: a coarse-to-fine search around every seed with a continuous
+    rule, the strip read at the fractional lag with linear interpolation (``zoom_terms``).
+
+    A level has a centre and a half-extent per axis; its Z^3 points are ``grid_points(ctr - half, ctr + half, (Z, Z, Z))`` (the same
+    arithmetic and linear index; a box that many levels have shrunk to a point is still a level: every cell ties, index 0 wins).  Level 0:
+    the seed's (x, y, z) and ``half0[3]`` in metres.  The next level has the best cell's centre and the half-extent ``(hi - lo) / Z``,
+    one cell: its box covers the best cell and half of each neighbour, and extents shrink by Z / 2 per level.  Where every cell of a
+    level is NaN the zoom stops: the record keeps the centre that level started from, ``power`` = NaN and ``levels`` = the levels
+    completed before it.  ``clipped`` counts the clipped terms over all cells of all levels run.  A seed with ``index < 0`` is absent:
+    ``seed`` = -1 and all else 0.
+
+    The order of the sum, ``tile_order``, is part of the rule: the device equals this byte for byte on any strips, so a last-bit
+    difference can never send the two down different paths.  ``T = half_width(...)`` still clips nothing: |q| <= T - 1 gives
+    -(T - 1) <= k <= T - 1.  ``return_levels``: also, per seed, the list of (centre[3], power) after every completed level."""
+    st = np.asarray(strips_, dtype=np.float64)
+    m = _mics(mics)
+    T, Z, levels = int(T), int(Z), int(levels)
+    npairs = m.shape[0] * (m.shape[0] - 1) // 2
+    if T < 1 or st.shape != (npairs, 2 * T + 1):
+        raise ValueError("strips must be [P][2T + 1] with T >= 1")
+    if not (fs > 0 and c > 0):
+        raise ValueError("fs and c must be positive")
+    if not 2 <= Z <= MAX_ZOOM_CELLS or not 1 <= levels <= MAX_ZOOM_LEVELS:
+        raise ValueError(f"need Z in 2..{MAX_ZOOM_CELLS} and levels in 1..{MAX_ZOOM_LEVELS}")
+    half0 = np.asarray(half0, dtype=np.float64).reshape(-1)
+    if half0.shape != (3,) or not np.all(np.isfinite(half0)) or np.any(half0 <= 0):
+        raise ValueError("half0 has three finite positive entries")
+    sd = np.asarray(seeds, dtype=PEAK).reshape(-1)
+    if not 1 <= sd.shape[0] <= MAX_PEAKS:
+        raise ValueError(f"K outside 1..{MAX_PEAKS}")
+    w = None if pair_weights is None else np.asarray(pair_weights, dtype=np.float64).reshape(npairs)
+    order = tile_order(m.shape[0])
+    out = np.zeros(sd.shape[0], dtype=ZOOM)
+    trail = []
+    for n, seed in enumerate(sd):
+        trail.append([])
+        if seed["index"] < 0:
+            out[n]["seed"] = -1
+            continue
+        ctr, half = np.array([seed["x"], seed["y"], seed["z"]], dtype=np.float64), half0.copy()
+        power, done, clipped = np.float64(0.0), 0, 0
+        for _ in range(levels):
+            acc, clip, best, pts = zoom_level(st, T, m, fs, c, ctr, half, Z, w, order)
+            clipped += clip
+            if best < 0:
+                power = np.float64(np.nan)
+                break
+            lo, hi = zoom_box(ctr, half)
+            with np.errstate(invalid="ignore", over="ignore"):
+                ctr, half, power = pts[best].copy(), zoom_next_half(lo, hi, Z), acc[best]
+            done += 1
+            trail[-1].append((ctr.copy(), float(power)))
+        out[n] = (ctr[0], ctr[1], ctr[2], power, clipped, seed["index"], done)
+    return (out, trail) if return_levels else out
 
 
 def peak_marks(power, R: int) -> np.ndarray:

@@ -4,13 +4,16 @@
 
     python tools/bench_srp.py [frames=128] [mics=64] [grid=64] [repeats=5] [spec_grid=16]
 
-Writes one JSON to profiles/srp_bench.json and prints it.  Every time is the best of `repeats` calls that end in synchronize, after a
+Writes one JSON to profiles/srp_bench.json, the zoom's to profiles/srp_zoom_bench.json, and prints both.  Every time is the best of `repeats` calls that end in synchronize, after a
 warm-up call, on buffers resident in HBM; kernel times are pal_profile's.
 - the strips call beside the one-peak call and the K = 4 call on the same frames (pairs/s);
 - the map (K = 1 peak per frame) in lag evaluations per second (G * P per frame) and in strip bytes read per second (8 B per
   evaluation), with its square roots per cell beside its lags per cell;
 - the NumPy specification (srp.srp_map) per frame on a `spec_grid`^3 grid of the same box, and whether the device's map of that grid
   equals it within the rounding bound and its peak index exactly.
+- the zoom (pal_srp_zoom_dev, Z = 8, three levels, the first box one map cell on each side of the seed) alone at K = 1 and K = 2 on the
+  peaks of the `grid`^3 map, and the `grid`^3 map alone against a (`grid` / 2)^3 map plus the zoom on the same strips: seconds, and the
+  median and worst distance of the answer from the frame's source.
 Frames: per frame one source inside the box, a common noise sequence delayed per microphone by the rounded path difference, plus
 independent noise of half its amplitude - host work, not timed."""
 import json
@@ -80,6 +83,57 @@ summ = eng.download(np.zeros(frames, dtype=_ffi.SRP_FRAME), dev["summary"])
 pos = np.stack([peaks["x"][:, 0], peaks["y"][:, 0], peaks["z"][:, 0]], axis=1)
 dist = np.linalg.norm(pos - sources, axis=1)
 
+# the zoom: alone on the fine map's peaks, and behind a map of half the resolution
+ZOOM_Z, ZOOM_LEVELS = 8, 3
+coarse = (max(grid_n // 2, 1),) * 3
+cell = lambda cnt: (np.asarray(hi) - np.asarray(lo)) / np.asarray(cnt, dtype=np.float64)  # noqa: E731
+dev_z = {"peaks2": eng.alloc(frames * 2 * _ffi.SRP_PEAK.itemsize), "zoom": eng.alloc(frames * 2 * _ffi.SRP_ZOOM.itemsize)}
+
+
+def zoom_distances(k):
+    z = eng.download(np.zeros((frames, k), dtype=_ffi.SRP_ZOOM), dev_z["zoom"])
+    d = np.linalg.norm(np.stack([z["x"], z["y"], z["z"]], axis=2) - sources[:, None, :], axis=2)
+    d = np.where(z["seed"] >= 0, d, np.inf).min(axis=1)                                # the seed that ends nearest the source
+    return {"median": round(float(np.median(d)), 4), "max": round(float(d.max()), 4)}, z
+
+
+zoom_rows = {}
+for k in (1, 2):
+    eng.srp_map_dev(dev["strips"], frames, T, mics, fs, c, lo, hi, count, 0, k, 1, dev["power"], dev_z["peaks2"], 0)
+    eng.synchronize()
+    t_z, k_z = best_of(lambda: (eng.srp_zoom_dev(dev["strips"], frames, T, mics, fs, c, dev_z["peaks2"], k, cell(count), ZOOM_Z, ZOOM_LEVELS,
+                                                 dev_z["zoom"]), eng.synchronize()))
+    dz, rec = zoom_distances(k)
+    zoom_rows[f"K{k}"] = {"seconds_per_call": round(t_z, 6), "kernels": {n: v for n, v in k_z.items() if n.startswith("k_srp")},
+                          "seeds": int(np.count_nonzero(rec["seed"] >= 0)), "clipped_terms": int(rec["clipped"].sum()),
+                          "levels_completed_min": int(rec["levels"][rec["seed"] >= 0].min()), "nearest_zoomed_to_source_m": dz}
+
+
+def coarse_then_zoom():
+    eng.srp_map_dev(dev["strips"], frames, T, mics, fs, c, lo, hi, coarse, 0, 1, 1, dev["power"], dev_z["peaks2"], 0)
+    eng.srp_zoom_dev(dev["strips"], frames, T, mics, fs, c, dev_z["peaks2"], 1, cell(coarse), ZOOM_Z, ZOOM_LEVELS, dev_z["zoom"])
+    eng.synchronize()
+
+
+t_cz, k_cz = best_of(coarse_then_zoom)
+d_cz, _ = zoom_distances(1)
+coarse_peaks = eng.download(np.zeros((frames, 1), dtype=_ffi.SRP_PEAK), dev_z["peaks2"])
+d_coarse = np.linalg.norm(np.stack([coarse_peaks["x"][:, 0], coarse_peaks["y"][:, 0], coarse_peaks["z"][:, 0]], axis=1) - sources, axis=1)
+for d in dev_z.values():
+    eng.free(d)
+zoom_out = {
+    "workload": {"frames": frames, "mics": mics_n, "pairs": P, "fs": fs, "half_width_T": T, "smoothing_W": W, "box_lo": lo, "box_hi": hi,
+                 "repeats": repeats, "Z": ZOOM_Z, "levels": ZOOM_LEVELS, "cells_per_seed": ZOOM_LEVELS * ZOOM_Z ** 3,
+                 "first_half_extent": "one cell of the map that gave the seeds"},
+    "zoom_alone_on_fine_map_peaks": zoom_rows,
+    "fine_map_alone": {"grid": list(count), "seconds_per_call": round(t_map, 6), "cell_m": round((hi[0] - lo[0]) / grid_n, 4),
+                       "first_peak_to_source_m": {"median": round(float(np.median(dist)), 4), "max": round(float(dist.max()), 4)}},
+    "coarse_map_plus_zoom": {"grid": list(coarse), "seconds_per_call": round(t_cz, 6), "cell_m": round((hi[0] - lo[0]) / coarse[0], 4),
+                             "kernels": {n: v for n, v in k_cz.items() if n.startswith("k_srp")},
+                             "coarse_first_peak_to_source_m": {"median": round(float(np.median(d_coarse)), 4), "max": round(float(d_coarse.max()), 4)},
+                             "zoomed_to_source_m": d_cz},
+}
+
 # the specification on a grid small enough to time, against the device's map of that grid
 strips0 = eng.download(np.zeros((P, width)), dev["strips"])                           # frame 0
 t0 = time.perf_counter()
@@ -115,5 +169,9 @@ os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
 with open(os.path.join(ROOT, "profiles", "srp_bench.json"), "w") as fh:
     json.dump(out, fh, indent=1)
     fh.write("\n")
+with open(os.path.join(ROOT, "profiles", "srp_zoom_bench.json"), "w") as fh:
+    json.dump(zoom_out, fh, indent=1)
+    fh.write("\n")
 print(json.dumps(out))
+print(json.dumps(zoom_out))
 eng.close()

@@ -344,6 +344,32 @@ int pal_tdoa_consensus(pal_handle h, const pal_pair_record* tables, const int32_
  *   finite and > 0, microphone coordinates finite, fs > 0, c > 0, M >= 2, B >= 1, no NULL buffer but d_pair_weights: PAL_ERR_INVALID
  *   otherwise; M > 4096: PAL_ERR_UNSUPPORTED.
  *
+ * pal_srp_doa*: the direction map, for arrays that resolve direction and not range: strips[B][P][2T+1] -> power[B][G] over
+ *   G = n_az * n_el directions under the plane-wave model.  The device evaluates no sine: az[n_az][2] = (cos, sin) of every azimuth and
+ *   el[n_el][2] = (cos, sin) of every elevation are host tables (srp.doa_axes builds them at the cell centres).  Cell (ia, ie) has the
+ *   linear index g = ia * n_el + ie and the direction ux = ce * ca, uy = ce * sa, uz = se; the entries must be finite, not unit vectors.
+ *     a_m = ux * mx; a_m += uy * my; a_m += uz * mz   (every product rounded),   s(g, p) = rint(((a_i - a_j) * fs) / c)   for p = (i, j)
+ *     power[g] = sum over p of w_p * strips[p][T + s(g, p)]
+ *   with the clip rule and the counters of pal_srp_map, the terms added in the order of the map kernel's microphone tiles
+ *   (srp.tile_order): the bytes are the specification's (srp.doa_map) on any strips, whatever B is.  With K > 0 the first K peaks of
+ *   every frame's map go to peaks[B][K] (see pal_srp_doa_peaks).  power, peaks and summary may each be NULL, not all; peaks needs K > 0.
+ *   mics, grid, az and el are host memory in both forms, read before the call returns.
+ *   1 <= n_az, n_el <= 1024 (PAL_ERR_INVALID below 1, PAL_ERR_UNSUPPORTED above), table entries and microphone coordinates finite,
+ *   fs > 0, c > 0, 0 <= K <= PAL_SRP_MAX_PEAKS, 1 <= R <= PAL_SRP_MAX_RADIUS when K > 0, T >= 0, M >= 2 (M > 4096:
+ *   PAL_ERR_UNSUPPORTED), B >= 1.
+ *
+ * pal_srp_doa_peaks*: power[B][n_az][n_el] -> peaks[B][K].  Cell (ia, ie) is a peak iff it is not NaN and no cell at offsets (da, de)
+ *   in -R..R is higher, or equal with a lower linear index; elevation is cut at the border, azimuth is taken mod n_az when
+ *   grid->wrap != 0 and cut otherwise.  Order, absent entries and summary as pal_srp_peaks; a record's x, y, z is the cell's direction.
+ *
+ * pal_srp_doa_zoom*: the zoom on the sphere (srp.doa_zoom), again without trigonometry.  A level has a centre u and one half-extent h
+ *   in tangent units (radians for small h); level 0 takes the seed's (x, y, z) as given and half0.  e1 = (k x u) / |k x u| with k the
+ *   coordinate axis of the smallest |u_k| (the lowest axis wins ties), e2 = u x e1; the offsets are the cell centres of -h .. h in Z
+ *   cells; cell (i, j), index i * Z + j, has the point (u + off_i e1 + off_j e2) / |..|, and its power sums pal_srp_zoom's interpolated
+ *   term at q = ((a_i - a_j) * fs) / c in tile order.  Best cell, next level (that point, half-extent 2h / Z), stop rule, absent seeds
+ *   and the record are pal_srp_zoom's, the record's x, y, z being the direction.  A seed whose direction is zero or not finite gives
+ *   what this arithmetic gives.  2 <= Z <= 16, 1 <= levels <= 16, 1 <= K <= 8, T >= 1, half0 finite and > 0: PAL_ERR_INVALID otherwise.
+ *
  * The _dev forms are asynchronous on the engine's stream (results complete after pal_synchronize); every `d_` pointer comes from
  * pal_device_alloc.  Every argument check is made before any buffer is touched. */
 #define PAL_SRP_MAX_SMOOTH 32
@@ -393,6 +419,27 @@ int pal_srp_zoom_dev(pal_handle h, const double* d_strips, int B, int M, int T, 
 int pal_srp_zoom(pal_handle h, const double* strips, int B, int M, int T, const double* mics, double fs, double c,
                  const double* pair_weights, const pal_srp_peak* seeds, int K, const double* half0, int Z, int levels,
                  pal_srp_zoom_record* out);
+typedef struct pal_srp_doa_grid {   /* 16 bytes */
+  int32_t n_az, n_el;     /* azimuths and elevations: the lengths of the two tables                */
+  int32_t wrap;           /* != 0: the azimuths close the circle, the peak rule takes them mod n_az */
+  int32_t reserved;
+} pal_srp_doa_grid;
+int pal_srp_doa_dev(pal_handle h, const double* d_strips, int B, int M, int T, const double* mics, double fs, double c,
+                    const pal_srp_doa_grid* grid, const double* az, const double* el, const double* d_pair_weights, int K, int R,
+                    double* d_power, pal_srp_peak* d_peaks, pal_srp_frame* d_summary);
+int pal_srp_doa(pal_handle h, const double* strips, int B, int M, int T, const double* mics, double fs, double c,
+                const pal_srp_doa_grid* grid, const double* az, const double* el, const double* pair_weights, int K, int R, double* power,
+                pal_srp_peak* peaks, pal_srp_frame* summary);
+int pal_srp_doa_peaks_dev(pal_handle h, const double* d_power, int B, const pal_srp_doa_grid* grid, const double* az, const double* el,
+                          int K, int R, pal_srp_peak* d_peaks, pal_srp_frame* d_summary);
+int pal_srp_doa_peaks(pal_handle h, const double* power, int B, const pal_srp_doa_grid* grid, const double* az, const double* el, int K,
+                      int R, pal_srp_peak* peaks, pal_srp_frame* summary);
+int pal_srp_doa_zoom_dev(pal_handle h, const double* d_strips, int B, int M, int T, const double* mics, double fs, double c,
+                         const double* d_pair_weights, const pal_srp_peak* d_seeds, int K, double half0, int Z, int levels,
+                         pal_srp_zoom_record* d_out);
+int pal_srp_doa_zoom(pal_handle h, const double* strips, int B, int M, int T, const double* mics, double fs, double c,
+                     const double* pair_weights, const pal_srp_peak* seeds, int K, double half0, int Z, int levels,
+                     pal_srp_zoom_record* out);
 
 /* single-pair signatures: phat_correlation(sig1, sig2) (utils.py:108) -> corr[n1+n2-1] */
 int pal_phat_correlation(pal_handle h, const double* sig1, int n1, const double* sig2, int n2, double* corr);

@@ -37,6 +37,13 @@ class SrpGrid(C.Structure):                                             # pal_sr
 
 
 assert C.sizeof(SrpGrid) == 64
+
+
+class SrpDoaGrid(C.Structure):                                          # pal_srp_doa_grid, 16 bytes
+    _fields_ = [("n_az", C.c_int32), ("n_el", C.c_int32), ("wrap", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(SrpDoaGrid) == 16
 # pal_srp_peak (40 bytes) and pal_srp_frame (16 bytes)
 SRP_PEAK = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("power", "<f8"), ("index", "<i4"), ("reserved", "<i4")])
 SRP_FRAME = np.dtype([("clipped", "<i8"), ("n_peaks", "<i4"), ("reserved", "<i4")])
@@ -46,6 +53,7 @@ SRP_MAX_SMOOTH, SRP_MAX_PEAKS, SRP_MAX_RADIUS = 32, 8, 4
 SRP_ZOOM = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("power", "<f8"), ("clipped", "<i8"), ("seed", "<i4"), ("levels", "<i4")])
 assert SRP_ZOOM.itemsize == 48
 SRP_MAX_ZOOM_CELLS, SRP_MAX_ZOOM_LEVELS = 16, 16
+SRP_MAX_DOA_COUNT = 1024                                                # azimuths, and elevations, of a direction grid
 
 # one row of the TDOA table (pal_pair_record, 48 bytes)
 RECORD = np.dtype([("k_sel", "<i4"), ("branch", "<i4"), ("k_argmax", "<i4"), ("n_sel", "<i4"),
@@ -127,6 +135,18 @@ SIGNATURES = {
                                    C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "pal_srp_zoom": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "pal_srp_doa_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.POINTER(SrpDoaGrid),
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pal_srp_doa": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.POINTER(SrpDoaGrid),
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pal_srp_doa_peaks_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(SrpDoaGrid), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p]),
+    "pal_srp_doa_peaks": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(SrpDoaGrid), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p]),
+    "pal_srp_doa_zoom_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]),
+    "pal_srp_doa_zoom": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]),
     "pal_phat_correlation": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "pal_get_time_delays_phat": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(PhatParams), C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

@@ -262,6 +262,18 @@ struct Engine {
   int srp_zoom_check(int B, int M, int T, const double* mics, double fs, double c, int K, const double* half0, int Z, int levels);
   int srp_zoom_dev(const double* d_strips, int B, int M, int T, const double* mics, double fs, double c, const double* d_pair_weights,
                    const pal_srp_peak* d_seeds, int K, const double* half0, int Z, int levels, pal_srp_zoom_record* d_out);
+  // the direction map, its peaks and its zoom (k_srp_doa, k_srp_doa_peaks, k_srp_doa_zoom): `mics`, `grid`, `az` and `el` are host memory
+  int srp_doa_check(int B, int M, int T, const double* mics, double fs, double c, const pal_srp_doa_grid* grid, const double* az,
+                    const double* el, int K, int R, bool any_output, bool peaks_out);
+  int srp_doa_dev(const double* d_strips, int B, int M, int T, const double* mics, double fs, double c, const pal_srp_doa_grid* grid,
+                  const double* az, const double* el, const double* d_pair_weights, int K, int R, double* d_power, pal_srp_peak* d_peaks,
+                  pal_srp_frame* d_summary);
+  int srp_doa_peaks_check(int B, const pal_srp_doa_grid* grid, const double* az, const double* el, int K, int R);
+  int srp_doa_peaks_dev(const double* d_power, int B, const pal_srp_doa_grid* grid, const double* az, const double* el, int K, int R,
+                        pal_srp_peak* d_peaks, pal_srp_frame* d_summary);
+  int srp_doa_zoom_check(int B, int M, int T, const double* mics, double fs, double c, int K, double half0, int Z, int levels);
+  int srp_doa_zoom_dev(const double* d_strips, int B, int M, int T, const double* mics, double fs, double c, const double* d_pair_weights,
+                       const pal_srp_peak* d_seeds, int K, double half0, int Z, int levels, pal_srp_zoom_record* d_out);
   int32_t* solve_idx = nullptr;    // device table pair -> i | j << 16 of the last microphone count
   int solve_idx_M = 0;
   // resample.hip: the right wing of the interpolation filter as pal_resample_set_filter received it, and the ratio whose scaled

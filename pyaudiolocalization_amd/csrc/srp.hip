@@ -18,7 +18,8 @@
 //                  floating-point atomics, no waits between workgroups, no scratch;
 //   k_srp_peaks    one workgroup of 1024 per frame over the stored map: marks the peaks by the neighbourhood rule (one byte per cell in
 //                  engine scratch), then K selection passes, each the block maximum - in the order power descending, index ascending - of
-//                  the marks behind the previous pass's pick; writes peaks[B][K] and the frame's summary;
+//                  the marks behind the previous pass's pick; writes peaks[B][K] and the frame's summary.  The passes are
+//                  srp_select.h's, shared with the direction map's k_srp_doa_peaks (srp_doa.hip);
 //   k_srp_zoom     one workgroup of 256 per (frame, seed) runs every level of the coarse-to-fine zoom (srp.zoom): a level's Z^3 cells in
 //                  chunks of 256, one lane per cell, with k_srp_map's tile scheme and the strip read at the fractional lag (two samples,
 //                  blended); the level's best cell by one block reduction, the next box through LDS.  The cell body is a second copy
@@ -27,6 +28,7 @@
 #include "closure_tiles.h"
 #include "engine.h"
 #include "srp_math.h"
+#include "srp_select.h"
 #include "wave_reduce.h"
 
 namespace pal {
@@ -36,8 +38,6 @@ static_assert(kSrpMaxSmooth == PAL_SRP_MAX_SMOOTH && kSrpMaxPeaks == PAL_SRP_MAX
 static_assert(sizeof(pal_srp_grid) == 64 && sizeof(pal_srp_peak) == 40 && sizeof(pal_srp_frame) == 16, "record sizes of pal_hip.h");
 static_assert(kSrpMaxZoomCells == PAL_SRP_MAX_ZOOM_CELLS && kSrpMaxZoomLevels == PAL_SRP_MAX_ZOOM_LEVELS, "the zoom's limits");
 static_assert(sizeof(pal_srp_zoom_record) == 48, "record size of pal_hip.h");
-constexpr int kSrpThreads = 256;
-constexpr int kSrpPeakThreads = 1024;
 
 struct SrpStripArgs {
   const double* rows;   // [nrows][n]
@@ -149,58 +149,14 @@ __global__ __launch_bounds__(kSrpPeakThreads) void k_srp_peaks(SrpPeakArgs a) {
     }
   }
   __syncthreads();
-  double prev_p = 0.0;
-  int prev_g = -1, found = 0;
-  for (int k = 0; k < a.K; ++k) {
-    double my_p = 0.0;
-    int my_g = -1;
-    if (k == 0 || prev_g >= 0) {
-      for (int g = tid; g < G; g += kSrpPeakThreads) {
-        if (!marks[g]) continue;
-        const double p = power[g];
-        if (k > 0 && !srp_before(prev_p, prev_g, p, g)) continue;       // taken by an earlier pass
-        if (my_g < 0 || srp_before(p, g, my_p, my_g)) { my_p = p; my_g = g; }
-      }
-    }
-    best_p[tid] = my_p;
-    best_g[tid] = my_g;
-    __syncthreads();
-    for (int half = kSrpPeakThreads / 2; half > 0; half >>= 1) {
-      if (tid < half) {
-        const int og = best_g[tid + half];
-        const double op = best_p[tid + half];
-        if (og >= 0 && (best_g[tid] < 0 || srp_before(op, og, best_p[tid], best_g[tid]))) { best_p[tid] = op; best_g[tid] = og; }
-      }
-      __syncthreads();
-    }
-    prev_p = best_p[0];
-    prev_g = best_g[0];
-    __syncthreads();                               // everyone has read the pick before the next pass overwrites it
-    if (prev_g >= 0) ++found;
-    if (tid == 0 && a.peaks) {
-      pal_srp_peak rec;
-      rec.x = rec.y = rec.z = rec.power = 0.0;
-      rec.index = -1;
-      rec.reserved = 0;
-      if (prev_g >= 0) {
-        int ix, iy, iz;
-        srp_cell(prev_g, a.ny, a.nz, ix, iy, iz);
-        rec.x = srp_coord(a.lo[0], a.step[0], ix);
-        rec.y = srp_coord(a.lo[1], a.step[1], iy);
-        rec.z = srp_coord(a.lo[2], a.step[2], iz);
-        rec.power = prev_p;
-        rec.index = prev_g;
-      }
-      a.peaks[size_t(b) * size_t(a.K) + k] = rec;
-    }
-  }
-  if (tid == 0 && a.summary) {
-    pal_srp_frame s;
-    s.clipped = a.clipped ? int64_t(a.clipped[b]) : 0;
-    s.n_peaks = found;
-    s.reserved = 0;
-    a.summary[b] = s;
-  }
+  srp_select_peaks(power, marks, G, a.K, a.peaks ? a.peaks + size_t(b) * size_t(a.K) : nullptr, a.summary ? a.summary + b : nullptr,
+                   a.clipped ? a.clipped + b : nullptr, best_p, best_g, [&](int g, pal_srp_peak& rec) {
+                     int ix, iy, iz;
+                     srp_cell(g, a.ny, a.nz, ix, iy, iz);
+                     rec.x = srp_coord(a.lo[0], a.step[0], ix);
+                     rec.y = srp_coord(a.lo[1], a.step[1], iy);
+                     rec.z = srp_coord(a.lo[2], a.step[2], iz);
+                   });
 }
 
 struct SrpZoomArgs {

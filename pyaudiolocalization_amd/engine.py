@@ -391,12 +391,8 @@ class Engine:
         g.reserved = 0
         return g
 
-    def srp_map(self, strips, mic_positions, fs, c, lo, hi, count, pair_weights=None, K: int = 0, R: int = 1,
-                outputs=("power", "peaks", "summary")):
-        """strips[B][P][2T+1] (or [P][2T+1]) -> (power[B][G], peaks[B][K] of _ffi.SRP_PEAK, summary[B] of _ffi.SRP_FRAME): the steered-
-        response power of every cell of the grid ``count`` cells over the box ``lo .. hi`` (g = (ix * ny + iy) * nz + iz), optionally
-        weighted per pair, the first ``K`` (0..8) peaks of each map within the neighbourhood radius ``R`` (1..4 cells) and the clipped
-        terms - see srp.srp_map and srp.map_peaks.  ``outputs``: the names to compute; the others (and ``peaks`` when K = 0) are None."""
+    @staticmethod
+    def _srp_inputs(strips, mic_positions, pair_weights):
         st = f64(strips)
         if st.ndim == 2:
             st = st[None]
@@ -405,11 +401,21 @@ class Engine:
         mics = f64(mic_positions)
         if mics.ndim != 2 or mics.shape[1] != 3:
             raise ValueError("mic_positions must be [M][3]")
-        b, p, width = st.shape
+        b, p, _ = st.shape
         m = mics.shape[0]
         if m >= 2 and p != m * (m - 1) // 2:
             raise ValueError(f"strips of {m} microphones have {m * (m - 1) // 2} rows per frame, got {p}")
-        wt = None if pair_weights is None else f64(pair_weights).reshape(b, p)
+        return st, mics, None if pair_weights is None else f64(pair_weights).reshape(b, p)
+
+    def srp_map(self, strips, mic_positions, fs, c, lo, hi, count, pair_weights=None, K: int = 0, R: int = 1,
+                outputs=("power", "peaks", "summary")):
+        """strips[B][P][2T+1] (or [P][2T+1]) -> (power[B][G], peaks[B][K] of _ffi.SRP_PEAK, summary[B] of _ffi.SRP_FRAME): the steered-
+        response power of every cell of the grid ``count`` cells over the box ``lo .. hi`` (g = (ix * ny + iy) * nz + iz), optionally
+        weighted per pair, the first ``K`` (0..8) peaks of each map within the neighbourhood radius ``R`` (1..4 cells) and the clipped
+        terms - see srp.srp_map and srp.map_peaks.  ``outputs``: the names to compute; the others (and ``peaks`` when K = 0) are None."""
+        st, mics, wt = self._srp_inputs(strips, mic_positions, pair_weights)
+        b, _, width = st.shape
+        m = mics.shape[0]
         grid = self._srp_grid(lo, hi, count)
         k = int(K)
         if any(name not in ("power", "peaks", "summary") for name in outputs):
@@ -464,23 +470,13 @@ class Engine:
         _ffi.SRP_ZOOM: a coarse-to-fine search around every seed, ``levels`` levels of ``Z``^3 cells, the first over the seed's position
         -+ ``half0[3]`` metres, each next one over the best cell and half of each neighbour, with the strip read at the fractional lag
         (linear interpolation) - see srp.zoom, which it equals byte for byte.  An absent seed (index -1) gives an absent record."""
-        st = f64(strips)
-        if st.ndim == 2:
-            st = st[None]
-        if st.ndim != 3 or st.shape[2] % 2 != 1:
-            raise ValueError("strips must be [P][2T+1] or [B][P][2T+1]")
-        mics = f64(mic_positions)
-        if mics.ndim != 2 or mics.shape[1] != 3:
-            raise ValueError("mic_positions must be [M][3]")
-        b, p, width = st.shape
+        st, mics, wt = self._srp_inputs(strips, mic_positions, pair_weights)
+        b, _, width = st.shape
         m = mics.shape[0]
-        if m >= 2 and p != m * (m - 1) // 2:
-            raise ValueError(f"strips of {m} microphones have {m * (m - 1) // 2} rows per frame, got {p}")
         sd = np.ascontiguousarray(seeds, dtype=_ffi.SRP_PEAK)
         if sd.size % b:
             raise ValueError("seeds must be [K] or [B][K]")
         sd = sd.reshape(b, -1)
-        wt = None if pair_weights is None else f64(pair_weights).reshape(b, p)
         h0 = f64(half0).reshape(-1)
         if h0.shape != (3,):
             raise ValueError("half0 has three entries")
@@ -502,6 +498,106 @@ class Engine:
         dev = [C.c_void_p(int(d)) if d else None for d in (d_strips, d_pair_weights, d_seeds, d_out)]
         self._check(self._lib.pal_srp_zoom_dev(self._h, dev[0], int(b), mics.shape[0], int(T), mics.ctypes.data, float(fs), float(c), dev[1],
                                                dev[2], int(K), h0.ctypes.data, int(Z), int(levels), dev[3]))
+
+    # ---- the direction map (specification: srp.py, doa_*) ------------------------------------------
+    @staticmethod
+    def _srp_doa_grid(az, el, wrap):
+        """-> (pal_srp_doa_grid, az[n_az][2], el[n_el][2]): the tables as the call reads them; their values are the call's to refuse."""
+        az, el = f64(az), f64(el)
+        if az.ndim != 2 or el.ndim != 2 or az.shape[1] != 2 or el.shape[1] != 2:
+            raise ValueError("az must be [n_az][2] and el [n_el][2]: (cos, sin)")
+        g = _ffi.SrpDoaGrid()
+        g.n_az, g.n_el, g.wrap, g.reserved = az.shape[0], el.shape[0], int(bool(wrap)), 0
+        return g, az, el
+
+    def srp_doa(self, strips, mic_positions, fs, c, az, el, wrap=1, pair_weights=None, K: int = 0, R: int = 1,
+                outputs=("power", "peaks", "summary")):
+        """strips[B][P][2T+1] (or [P][2T+1]) -> (power[B][n_az * n_el], peaks[B][K] of _ffi.SRP_PEAK, summary[B] of _ffi.SRP_FRAME): the
+        steered-response power of every direction of the grid given by the tables ``az[n_az][2]`` and ``el[n_el][2]`` of (cos, sin), as
+        srp.doa_axes builds them (g = ia * n_el + ie), under the plane-wave model, optionally weighted per pair; the first ``K`` (0..8)
+        peaks of each map within ``R`` (1..4) cells, azimuth taken mod n_az when ``wrap``, with the cells' directions in x, y, z; and the
+        clipped terms - see srp.doa_map and srp.doa_peaks, which it equals byte for byte.  ``outputs``: as in srp_map."""
+        st, mics, wt = self._srp_inputs(strips, mic_positions, pair_weights)
+        grid, az, el = self._srp_doa_grid(az, el, wrap)
+        b, k = st.shape[0], int(K)
+        if any(name not in ("power", "peaks", "summary") for name in outputs):
+            raise ValueError("outputs: 'power', 'peaks', 'summary'")
+        big = not (1 <= grid.n_az <= _ffi.SRP_MAX_DOA_COUNT and 1 <= grid.n_el <= _ffi.SRP_MAX_DOA_COUNT)        # the call refuses it
+        power = np.zeros((b, 1 if big else grid.n_az * grid.n_el), dtype=np.float64) if "power" in outputs else None
+        peaks = np.zeros((b, k), dtype=_ffi.SRP_PEAK) if "peaks" in outputs and 0 < k <= _ffi.SRP_MAX_PEAKS else None
+        summ = np.zeros(b, dtype=_ffi.SRP_FRAME) if "summary" in outputs else None
+        self._check(self._lib.pal_srp_doa(self._h, st.ctypes.data, b, mics.shape[0], (st.shape[2] - 1) // 2, mics.ctypes.data, float(fs),
+                                          float(c), C.byref(grid), az.ctypes.data, el.ctypes.data, ptr(wt), k, int(R), ptr(power), ptr(peaks),
+                                          ptr(summ)))
+        return power, peaks, summ
+
+    def srp_doa_dev(self, d_strips: int, b: int, T: int, mic_positions, fs, c, az, el, wrap=1, d_pair_weights: int = 0, K: int = 0,
+                    R: int = 1, d_power: int = 0, d_peaks: int = 0, d_summary: int = 0) -> None:
+        """Asynchronous: strips[b][P][2T+1], the optional pair_weights[b][P] and the requested outputs (0 = not wanted; at least one)
+        stay in HBM; ``mic_positions`` and the tables are read before the call returns."""
+        mics = f64(mic_positions)
+        if mics.ndim != 2 or mics.shape[1] != 3:
+            raise ValueError("mic_positions must be [M][3]")
+        grid, az, el = self._srp_doa_grid(az, el, wrap)
+        dev = [C.c_void_p(int(d)) if d else None for d in (d_strips, d_pair_weights, d_power, d_peaks, d_summary)]
+        self._check(self._lib.pal_srp_doa_dev(self._h, dev[0], int(b), mics.shape[0], int(T), mics.ctypes.data, float(fs), float(c),
+                                              C.byref(grid), az.ctypes.data, el.ctypes.data, dev[1], int(K), int(R), dev[2], dev[3], dev[4]))
+
+    def srp_doa_peaks(self, power, az, el, wrap=1, K: int = 1, R: int = 1):
+        """power[B][n_az][n_el] (or [n_az][n_el], or [B][G]) -> (peaks[B][K] of _ffi.SRP_PEAK, summary[B] of _ffi.SRP_FRAME): the first
+        ``K`` peaks of every direction map by the wrapped neighbourhood rule of radius ``R`` - see srp.doa_peaks."""
+        grid, az, el = self._srp_doa_grid(az, el, wrap)
+        cells = grid.n_az * grid.n_el
+        pw = f64(power)
+        ok = 1 <= grid.n_az <= _ffi.SRP_MAX_DOA_COUNT and 1 <= grid.n_el <= _ffi.SRP_MAX_DOA_COUNT                # otherwise the call refuses the grid
+        if ok:
+            if pw.size % cells:
+                raise ValueError("power does not hold whole maps of the grid")
+            pw = pw.reshape(-1, cells)
+        b = pw.shape[0] if ok else 1
+        k = int(K)
+        peaks = np.zeros((b, k if 0 < k <= _ffi.SRP_MAX_PEAKS else 1), dtype=_ffi.SRP_PEAK)
+        summ = np.zeros(b, dtype=_ffi.SRP_FRAME)
+        self._check(self._lib.pal_srp_doa_peaks(self._h, pw.ctypes.data, b, C.byref(grid), az.ctypes.data, el.ctypes.data, k, int(R),
+                                                peaks.ctypes.data, summ.ctypes.data))
+        return peaks, summ
+
+    def srp_doa_peaks_dev(self, d_power: int, b: int, az, el, wrap, K: int, R: int, d_peaks: int, d_summary: int = 0) -> None:
+        """Asynchronous: power[b][G], peaks[b][K] and the summary (0 = not wanted) stay in HBM."""
+        grid, az, el = self._srp_doa_grid(az, el, wrap)
+        self._check(self._lib.pal_srp_doa_peaks_dev(self._h, C.c_void_p(d_power) if d_power else None, int(b), C.byref(grid), az.ctypes.data,
+                                                    el.ctypes.data, int(K), int(R), C.c_void_p(d_peaks) if d_peaks else None,
+                                                    C.c_void_p(d_summary) if d_summary else None))
+
+    def srp_doa_zoom(self, strips, mic_positions, fs, c, seeds, half0, Z: int = 8, levels: int = 3, pair_weights=None):
+        """strips[B][P][2T+1] (or [P][2T+1]) and seeds[B][K] (or [K]) of _ffi.SRP_PEAK, as srp_doa returns its peaks -> out[B][K] of
+        _ffi.SRP_ZOOM with the direction in x, y, z: the zoom on the sphere, ``levels`` levels of ``Z``^2 directions, the first over the
+        seed's direction -+ ``half0`` (one number, radians for small values) in its tangent plane, each next one over the best cell and
+        half of each neighbour - see srp.doa_zoom, which it equals byte for byte.  An absent seed (index -1) gives an absent record."""
+        st, mics, wt = self._srp_inputs(strips, mic_positions, pair_weights)
+        b = st.shape[0]
+        sd = np.ascontiguousarray(seeds, dtype=_ffi.SRP_PEAK)
+        if sd.size % b:
+            raise ValueError("seeds must be [K] or [B][K]")
+        sd = sd.reshape(b, -1)
+        if np.ndim(half0) != 0:
+            raise ValueError("half0 is one number")
+        out = np.zeros(sd.shape, dtype=_ffi.SRP_ZOOM)
+        self._check(self._lib.pal_srp_doa_zoom(self._h, st.ctypes.data, b, mics.shape[0], (st.shape[2] - 1) // 2, mics.ctypes.data, float(fs),
+                                               float(c), ptr(wt), sd.ctypes.data, sd.shape[1], float(half0), int(Z), int(levels),
+                                               out.ctypes.data))
+        return out
+
+    def srp_doa_zoom_dev(self, d_strips: int, b: int, T: int, mic_positions, fs, c, d_seeds: int, K: int, half0, Z: int, levels: int,
+                         d_out: int, d_pair_weights: int = 0) -> None:
+        """Asynchronous: strips[b][P][2T+1], seeds[b][K], the optional pair_weights[b][P] and out[b][K] stay in HBM; ``mic_positions``
+        is read before the call returns."""
+        mics = f64(mic_positions)
+        if mics.ndim != 2 or mics.shape[1] != 3:
+            raise ValueError("mic_positions must be [M][3]")
+        dev = [C.c_void_p(int(d)) if d else None for d in (d_strips, d_pair_weights, d_seeds, d_out)]
+        self._check(self._lib.pal_srp_doa_zoom_dev(self._h, dev[0], int(b), mics.shape[0], int(T), mics.ctypes.data, float(fs), float(c),
+                                                   dev[1], dev[2], int(K), float(half0), int(Z), int(levels), dev[3]))
 
     def solve_positions(self, tables, lengths, mic_positions, fs, c, calib_delays=None, weights="ones", buffer=5.0, grid=solve.GRID,
                         max_iter=solve.MAX_ITER, extra_starts=None, loss="linear", f_scale=1.0, return_pair_weights=False,

@@ -253,6 +253,38 @@ def srp_positions_device(frames, mic_positions, fs, c, lo, hi, count, W=8, K=1, 
     return (peaks[0], rec[0]) if one else (peaks, rec)
 
 
+def srp_directions_device(frames, mic_positions, fs, c, n_az=72, n_el=36, W=2, K=1, R=1, T=None, pair_weights=None, zoom=None, engine=None,
+                          threshold_method="median", threshold_multiplier=1.0, max_expected_delay=None):
+    """frames[B][M][L] (or [M][L]) -> peaks[B][K] of _ffi.SRP_PEAK with directions in x, y, z: the first ``K`` maxima (neighbourhood
+    radius ``R`` cells, azimuth wrapped) of every frame's direction map over ``n_az`` x ``n_el`` cells
+    of azimuth and elevation (Engine.gcc_phat_all_pairs_strips with smoothing ``W``, then Engine.srp_doa; rules: srp.py, doa_*).  For
+    arrays that resolve direction and not range: a source far from the array lies on a two-dimensional set of directions, and a
+    5-degree sphere is 2592 cells.  ``T``: the strips' half-width, by default srp.half_width, for which no lag is clipped.
+    ``zoom=(Z, levels)`` or ``(Z, levels, span)``: Engine.srp_doa_zoom refines the K directions on the same strips, the first level
+    over each peak -+ ``span`` (default 1.0) cells of elevation in its tangent plane -> (peaks, zoomed[B][K] of _ffi.SRP_ZOOM).
+    srp.doa_angles turns either into degrees."""
+    from . import srp
+    eng = engine or default_engine()
+    x = np.ascontiguousarray(frames, dtype=np.float64)
+    one = x.ndim == 2
+    if one:
+        x = x[None]
+    if x.ndim != 3:
+        raise ValueError("frames must be [M][L] or [B][M][L]")
+    mics = np.ascontiguousarray(mic_positions, dtype=np.float64)
+    az, el, wrap = srp.doa_axes(n_az, n_el)                                             # the full sphere: azimuth wraps
+    half = srp.half_width(mics, fs, c) if T is None else int(T)
+    strips, _ = eng.gcc_phat_all_pairs_strips(x, fs, half, W, threshold_method, threshold_multiplier, max_expected_delay, want_table=False)
+    peaks = eng.srp_doa(strips, mics, fs, c, az, el, wrap, pair_weights, K, R, outputs=("peaks",))[1]
+    if zoom is None:
+        return peaks[0] if one else peaks
+    if len(zoom) not in (2, 3):
+        raise ValueError("zoom is (Z, levels) or (Z, levels, span)")
+    span = float(zoom[2]) if len(zoom) == 3 else 1.0
+    zoomed = eng.srp_doa_zoom(strips, mics, fs, c, peaks, span * (np.pi / int(n_el)), int(zoom[0]), int(zoom[1]), pair_weights)
+    return (peaks[0], zoomed[0]) if one else (peaks, zoomed)
+
+
 def localize_sound_source(config, calibration_data=None, audio_files=None, use_simulation=True, show_plots=True):
     fs = config["fs"]
     duration = config["duration"]

@@ -20,7 +20,9 @@ index mapping plays no part, and several sources show as several maxima.  Conven
   index;
 - the map is piecewise constant in space (``rint`` picks one sample), so below about c / fs a finer grid finds plateaus.  The **zoom**
   (``zoom``) refines a peak with a continuous rule instead: the strip read at the fractional lag with linear interpolation, over small
-  boxes that shrink around the best cell, the terms added in the fixed order ``tile_order``.
+  boxes that shrink around the best cell, the terms added in the fixed order ``tile_order``;
+- the **direction map** (``doa_map``, ``doa_peaks``, ``doa_zoom``; pal_srp_doa*, csrc/srp_doa.hip) sums the same strips over a grid of
+  azimuth and elevation under the plane-wave model, for arrays that resolve direction and not range: see the section at the end.
 
 Every product is rounded before it is added (no fused multiply-add), square root and division are correctly rounded and rint rounds
 half to even, so the device's grid points, lags, clip decisions, smoothing sums and peak marks equal these bit for bit.  The order of
@@ -32,6 +34,7 @@ from __future__ import annotations
 import numpy as np
 
 from ._ffi import SRP_FRAME as FRAME                                   # pal_srp_frame
+from ._ffi import SRP_MAX_DOA_COUNT as MAX_DOA_COUNT                   # azimuths, and elevations, of a direction grid
 from ._ffi import SRP_MAX_PEAKS as MAX_PEAKS
 from ._ffi import SRP_MAX_RADIUS as MAX_RADIUS
 from ._ffi import SRP_MAX_SMOOTH as MAX_SMOOTH
@@ -198,9 +201,13 @@ def zoom_terms(strips_, T: int, points, mics, fs, c, pair_weights=None):
     ``q = ((d_j - d_i) * fs) / c``, ``k = floor(q)``, ``f = q - k``; clipped iff not (k >= -T and k <= T - 1), decided on the doubles;
     otherwise ``v = s0 + f * (s1 - s0)`` with ``s0 = strips[p][T + k]``, ``s1 = strips[p][T + k + 1]`` (the product rounded before the
     addition), then ``v = w_p * v``."""
+    return terms_at(strips_, T, lag_quotients(points, mics, fs, c), pair_weights)
+
+
+def terms_at(strips_, T: int, q, pair_weights=None):
+    """``zoom_terms`` from the quotients q[G][P] themselves, wherever they come from."""
     st = np.asarray(strips_, dtype=np.float64)
     T = int(T)
-    q = lag_quotients(points, mics, fs, c)
     with np.errstate(invalid="ignore"):
         k = np.floor(q)
         f = q - k
@@ -349,3 +356,269 @@ def map_peaks(power, K: int, R: int, lo=None, hi=None):
         for a, name in enumerate("xyz"):
             out[name][:order.shape[0]] = pts[order, a]
     return out
+
+
+# ---- the direction map: far-field azimuth / elevation power, its peaks and a zoom on the sphere (pal_srp_doa*) -------------------
+# The arrays this project runs on resolve direction, not range: everything the map can know about a far source lies on the sphere
+# of directions.  A source far away in the direction u reaches microphone m earlier than the origin by the advance a_m = u . m, so
+# d_j - d_i = a_i - a_j and the lag of pair (i, j) is rint(((a_i - a_j) * fs) / c).  The device evaluates no sine: the grid is two host
+# tables of (cos, sin), and the zoom works in the tangent plane of its centre.  The terms of every sum are added in ``tile_order``, so
+# the device equals these functions byte for byte on any strips.
+def doa_axes(n_az: int, n_el: int, az_lo=0.0, az_hi=2.0 * np.pi, el_lo=-0.5 * np.pi, el_hi=0.5 * np.pi):
+    """-> (az[n_az][2], el[n_el][2], wrap): (cos, sin) of the cell centres ``lo + (i + 0.5) * ((hi - lo) / n)`` of both axes, in radians.
+    ``wrap`` = 1 iff the azimuths span the full circle; with the default limits no cell centre sits on a pole."""
+    n_az, n_el = int(n_az), int(n_el)
+    if not (1 <= n_az <= MAX_DOA_COUNT and 1 <= n_el <= MAX_DOA_COUNT):
+        raise ValueError(f"n_az and n_el outside 1..{MAX_DOA_COUNT}")
+    lim = np.asarray([az_lo, az_hi, el_lo, el_hi], dtype=np.float64)
+    if not np.all(np.isfinite(lim)) or not (lim[1] > lim[0] and lim[3] > lim[2]):
+        raise ValueError("need finite limits with hi above lo")
+    out = []
+    for lo, hi, n in ((lim[0], lim[1], n_az), (lim[2], lim[3], n_el)):
+        a = lo + (np.arange(n, dtype=np.float64) + 0.5) * ((hi - lo) / np.float64(n))
+        out.append(np.ascontiguousarray(np.stack([np.cos(a), np.sin(a)], axis=1)))
+    return out[0], out[1], int(abs((lim[1] - lim[0]) - 2.0 * np.pi) <= 1e-12)
+
+
+def check_doa_tables(az, el):
+    """-> (az[n_az][2], el[n_el][2]) float64; ValueError as pal_srp_doa refuses them."""
+    az, el = np.ascontiguousarray(az, dtype=np.float64), np.ascontiguousarray(el, dtype=np.float64)
+    if az.ndim != 2 or el.ndim != 2 or az.shape[1] != 2 or el.shape[1] != 2:
+        raise ValueError("az must be [n_az][2] and el [n_el][2]: (cos, sin)")
+    if not (1 <= az.shape[0] <= MAX_DOA_COUNT and 1 <= el.shape[0] <= MAX_DOA_COUNT):
+        raise ValueError(f"n_az and n_el outside 1..{MAX_DOA_COUNT}")
+    if not (np.all(np.isfinite(az)) and np.all(np.isfinite(el))):
+        raise ValueError("a direction table entry is not finite")
+    return az, el
+
+
+def doa_directions(az, el) -> np.ndarray:
+    """u[G][3], g = ia * n_el + ie: ux = ce * ca, uy = ce * sa, uz = se."""
+    az, el = check_doa_tables(az, el)
+    ca, sa, ce, se = az[:, None, 0], az[:, None, 1], el[None, :, 0], el[None, :, 1]
+    u = np.stack([ce * ca, ce * sa, np.broadcast_to(se, (az.shape[0], el.shape[0]))], axis=2)
+    return np.ascontiguousarray(u.reshape(-1, 3))
+
+
+def doa_advances(directions, mics) -> np.ndarray:
+    """a[G][M]: a = ux*mx; a = a + uy*my; a = a + uz*mz."""
+    u, m = np.asarray(directions, dtype=np.float64).reshape(-1, 3), _mics(mics)
+    with np.errstate(invalid="ignore", over="ignore"):
+        a = u[:, None, 0] * m[None, :, 0]
+        a = a + u[:, None, 1] * m[None, :, 1]
+        a = a + u[:, None, 2] * m[None, :, 2]
+    return a
+
+
+def doa_lag_quotients(directions, mics, fs, c) -> np.ndarray:
+    """The unrounded lags ((a_i - a_j) * fs) / c as float64 [G][P]."""
+    a = doa_advances(directions, mics)
+    i, j = np.triu_indices(a.shape[1], k=1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return ((a[:, i] - a[:, j]) * np.float64(fs)) / np.float64(c)
+
+
+def doa_lag_margin(directions, mics, fs, c) -> float:
+    """``lag_margin`` of the direction map's lags."""
+    q = doa_lag_quotients(directions, mics, fs, c)
+    return float(np.min(np.abs(np.abs(q - np.floor(q)) - 0.5)))
+
+
+def _sum_in_tile_order(v, M):
+    acc = np.zeros(v.shape[0])
+    with np.errstate(invalid="ignore", over="ignore"):
+        for p in tile_order(M):
+            acc = acc + v[:, p]                                # v is 0.0 where clipped, and acc is never -0.0: adding it adds nothing
+    return acc
+
+
+def doa_map(strips_, T: int, mics, fs, c, az, el, pair_weights=None):
+    """strips[P][2T + 1] of one frame -> (power[G] float64, clipped int), G = n_az * n_el: ``power[g] = sum_p w_p * strips[p][T + s]``
+    with ``s = rint(((a_i - a_j) * fs) / c)`` (half to even), the terms added in ``tile_order``; a term with not |s| <= T is clipped:
+    it adds nothing and is counted.  ``T = half_width(...)`` clips nothing for unit directions: |a_i - a_j| <= |m_i - m_j|."""
+    st = np.asarray(strips_, dtype=np.float64)
+    m = _mics(mics)
+    T = int(T)
+    npairs = m.shape[0] * (m.shape[0] - 1) // 2
+    if T < 0 or st.shape != (npairs, 2 * T + 1):
+        raise ValueError("strips must be [P][2T + 1]")
+    if not (fs > 0 and c > 0):
+        raise ValueError("fs and c must be positive")
+    r = np.rint(doa_lag_quotients(doa_directions(az, el), m, fs, c))
+    out = ~(np.abs(r) <= T)
+    v = st[np.arange(npairs)[None, :], T + np.where(out, 0, r).astype(np.int64)]
+    with np.errstate(invalid="ignore", over="ignore"):
+        if pair_weights is not None:
+            v = np.asarray(pair_weights, dtype=np.float64).reshape(1, npairs) * v
+    return _sum_in_tile_order(np.where(out, 0.0, v), m.shape[0]), int(np.count_nonzero(out))
+
+
+def doa_peak_marks(power, R: int, wrap) -> np.ndarray:
+    """bool [n_az][n_el]: cell (ia, ie) is a peak iff it is not NaN and no cell at offsets (da, de) in -R .. R is higher, or equal with
+    a lower linear index.  Elevation is cut at the border; azimuth is taken mod n_az when ``wrap`` and cut otherwise."""
+    p = np.asarray(power, dtype=np.float64)
+    if p.ndim != 2:
+        raise ValueError("power must be [n_az][n_el]")
+    R = int(R)
+    if not 1 <= R <= MAX_RADIUS:
+        raise ValueError(f"R outside 1..{MAX_RADIUS}")
+    n_az, n_el = p.shape
+    idx = np.arange(p.size, dtype=np.int64).reshape(p.shape)
+    rows = np.arange(n_az)
+    mark = ~np.isnan(p)
+    for da in range(-R, R + 1):
+        at = rows + da
+        inside = np.ones(n_az, dtype=bool) if wrap else (at >= 0) & (at < n_az)
+        at = np.mod(at, n_az)
+        for de in range(-R, R + 1):
+            o = np.full(p.shape, np.nan)                                                 # NaN: neither higher nor equal
+            oi = np.zeros(p.shape, dtype=np.int64)
+            e0, e1 = max(0, -de), min(n_el, n_el - de)                                   # the cells whose ie + de is inside
+            if e0 < e1:
+                o[:, e0:e1] = np.where(inside[:, None], p[at][:, e0 + de:e1 + de], np.nan)
+                oi[:, e0:e1] = idx[at][:, e0 + de:e1 + de]
+            mark &= ~((o > p) | ((o == p) & (oi < idx)))
+    return mark
+
+
+def doa_peaks(power, K: int, R: int, wrap, az=None, el=None):
+    """power[n_az][n_el] -> peaks[K] of PEAK: the first K peaks by power descending, then index; absent entries have index -1 and all
+    else 0.  With the tables the records carry the cells' directions, otherwise x = y = z = 0."""
+    p = np.asarray(power, dtype=np.float64)
+    K = int(K)
+    if not 1 <= K <= MAX_PEAKS:
+        raise ValueError(f"K outside 1..{MAX_PEAKS}")
+    mark = doa_peak_marks(p, R, wrap).reshape(-1)
+    flat = p.reshape(-1)
+    cand = np.flatnonzero(mark)
+    order = cand[np.lexsort((cand, -flat[cand]))][:K]
+    out = np.zeros(K, dtype=PEAK)
+    out["index"] = -1
+    out["index"][:order.shape[0]] = order
+    out["power"][:order.shape[0]] = flat[order]
+    if az is not None:
+        u = doa_directions(az, el)
+        if u.shape[0] != p.size:
+            raise ValueError("the tables do not match the map")
+        for a, name in enumerate("xyz"):
+            out[name][:order.shape[0]] = u[order, a]
+    return out
+
+
+def _norm3(x, y, z):
+    q = x * x
+    q = q + y * y
+    q = q + z * z
+    return np.sqrt(q)
+
+
+def doa_basis(u):
+    """-> (k, e1[3], e2[3]): the tangent basis of a level's centre.  k is the coordinate axis of the smallest |u_k|, the lowest axis
+    winning ties (a NaN is never smaller); ``e1 = (k x u) / |k x u|``: two copies or negations and a zero, each divided by the norm
+    ``q = ex*ex; q = q + ey*ey; q = q + ez*ez; sqrt(q)``; ``e2 = u x e1``, each component p1 - p2 of two rounded products."""
+    u = np.asarray(u, dtype=np.float64).reshape(3)
+    k, m = 0, abs(u[0])
+    if abs(u[1]) < m:
+        k, m = 1, abs(u[1])
+    if abs(u[2]) < m:
+        k = 2
+    zero = np.float64(0.0)
+    e = ((zero, -u[2], u[1]), (u[2], zero, -u[0]), (-u[1], u[0], zero))[k]
+    with np.errstate(all="ignore"):
+        n = _norm3(*e)
+        e1 = np.array([e[0] / n, e[1] / n, e[2] / n])
+        e2 = np.array([u[1] * e1[2] - u[2] * e1[1], u[2] * e1[0] - u[0] * e1[2], u[0] * e1[1] - u[1] * e1[0]])
+    return k, e1, e2
+
+
+def doa_zoom_offsets(half, Z: int) -> np.ndarray:
+    """off[Z]: the cell centres of -half .. half, ``-half + (i + 0.5) * ((half - (-half)) / Z)``."""
+    half = np.float64(half)
+    with np.errstate(all="ignore"):
+        return -half + (np.arange(int(Z), dtype=np.float64) + 0.5) * ((half - (-half)) / np.float64(int(Z)))
+
+
+def doa_zoom_points(u, half, Z: int) -> np.ndarray:
+    """points[Z^2][3], cell (i, j) at index i * Z + j: ``v = u + off_i * e1`` per component, then ``v = v + off_j * e2``, then ``v / |v|``."""
+    u = np.asarray(u, dtype=np.float64).reshape(3)
+    _, e1, e2 = doa_basis(u)
+    off = doa_zoom_offsets(half, Z)
+    oi, oj = np.meshgrid(off, off, indexing="ij")
+    with np.errstate(all="ignore"):
+        v = [u[a] + oi * e1[a] for a in range(3)]
+        v = [v[a] + oj * e2[a] for a in range(3)]
+        n = _norm3(*v)
+        return np.ascontiguousarray(np.stack([(v[a] / n).reshape(-1) for a in range(3)], axis=1))
+
+
+def doa_zoom_next_half(half, Z: int):
+    """The next level's half-extent: one cell of this level, (half - (-half)) / Z."""
+    half = np.float64(half)
+    with np.errstate(all="ignore"):
+        return (half - (-half)) / np.float64(int(Z))
+
+
+def doa_zoom_level(strips_, T: int, mics, fs, c, u, half, Z: int, pair_weights=None):
+    """One level -> (power[Z^2], clipped, best index or -1, points[Z^2][3]): the power of a point sums ``terms_at`` on the quotients
+    ``((a_i - a_j) * fs) / c`` of the point's advances in ``tile_order``; the best cell is the first by (power descending, index
+    ascending) among the cells that are not NaN."""
+    pts = doa_zoom_points(u, half, Z)
+    v, out, _, _, _ = terms_at(strips_, T, doa_lag_quotients(pts, mics, fs, c), pair_weights)
+    acc = _sum_in_tile_order(v, np.asarray(mics).shape[0])
+    ok = ~np.isnan(acc)
+    best = int(np.flatnonzero(ok & (acc == np.max(acc[ok])))[0]) if np.any(ok) else -1
+    return acc, int(np.count_nonzero(out)), best, pts
+
+
+def doa_zoom(strips_, T: int, mics, fs, c, seeds, half0, Z: int = 8, levels: int = 3, pair_weights=None, return_levels=False):
+    """strips[P][2T + 1] of one frame and seeds[K] of PEAK, as ``doa_peaks`` writes them -> out[K] of ZOOM with the direction in x, y, z:
+    the zoom on the sphere.  A level has a centre u and one half-extent h in tangent units (radians, for small h); its Z^2 points are
+    ``doa_zoom_points(u, h, Z)``.  Level 0: the seed's (x, y, z) as given, and ``half0``.  The next level has the best point as its
+    centre and ``doa_zoom_next_half(h, Z)``.  The stop rule, the absent-seed rule and the meaning of ``levels`` and ``clipped`` are
+    those of ``zoom``.  A seed whose direction is zero or not finite gives whatever this arithmetic gives.  ``return_levels``: also, per
+    seed, the list of (centre[3], power) after every completed level."""
+    st = np.asarray(strips_, dtype=np.float64)
+    m = _mics(mics)
+    T, Z, levels = int(T), int(Z), int(levels)
+    npairs = m.shape[0] * (m.shape[0] - 1) // 2
+    if T < 1 or st.shape != (npairs, 2 * T + 1):
+        raise ValueError("strips must be [P][2T + 1] with T >= 1")
+    if not (fs > 0 and c > 0):
+        raise ValueError("fs and c must be positive")
+    if not 2 <= Z <= MAX_ZOOM_CELLS or not 1 <= levels <= MAX_ZOOM_LEVELS:
+        raise ValueError(f"need Z in 2..{MAX_ZOOM_CELLS} and levels in 1..{MAX_ZOOM_LEVELS}")
+    half0 = np.asarray(half0, dtype=np.float64)
+    if half0.shape != () or not np.isfinite(half0) or half0 <= 0:
+        raise ValueError("half0 is one finite positive number")
+    sd = np.asarray(seeds, dtype=PEAK).reshape(-1)
+    if not 1 <= sd.shape[0] <= MAX_PEAKS:
+        raise ValueError(f"K outside 1..{MAX_PEAKS}")
+    w = None if pair_weights is None else np.asarray(pair_weights, dtype=np.float64).reshape(npairs)
+    out = np.zeros(sd.shape[0], dtype=ZOOM)
+    trail = []
+    for n, seed in enumerate(sd):
+        trail.append([])
+        if seed["index"] < 0:
+            out[n]["seed"] = -1
+            continue
+        ctr, half = np.array([seed["x"], seed["y"], seed["z"]], dtype=np.float64), np.float64(half0)
+        power, done, clipped = np.float64(0.0), 0, 0
+        for _ in range(levels):
+            acc, clip, best, pts = doa_zoom_level(st, T, m, fs, c, ctr, half, Z, w)
+            clipped += clip
+            if best < 0:
+                power = np.float64(np.nan)
+                break
+            ctr, half, power = pts[best].copy(), doa_zoom_next_half(half, Z), acc[best]
+            done += 1
+            trail[-1].append((ctr.copy(), float(power)))
+        out[n] = (ctr[0], ctr[1], ctr[2], power, clipped, seed["index"], done)
+    return (out, trail) if return_levels else out
+
+
+def doa_angles(records):
+    """(azimuth, elevation) in degrees of the directions in records' x, y, z (PEAK or ZOOM), by arctan2 on the host: azimuth in
+    0 .. 360, elevation in -90 .. 90.  For reporting only; no rule reads it."""
+    r = np.asarray(records)
+    x, y, z = (np.asarray(r[name], dtype=np.float64) for name in "xyz")
+    return np.mod(np.degrees(np.arctan2(y, x)), 360.0), np.degrees(np.arctan2(z, np.hypot(x, y)))

@@ -4,7 +4,8 @@
 
     python tools/bench_srp.py [frames=128] [mics=64] [grid=64] [repeats=5] [spec_grid=16]
 
-Writes one JSON to profiles/srp_bench.json, the zoom's to profiles/srp_zoom_bench.json, and prints both.  Every time is the best of `repeats` calls that end in synchronize, after a
+Writes one JSON to profiles/srp_bench.json, the zoom's to profiles/srp_zoom_bench.json, the direction map's to
+profiles/srp_doa_bench.json, and prints all three.  Every time is the best of `repeats` calls that end in synchronize, after a
 warm-up call, on buffers resident in HBM; kernel times are pal_profile's.
 - the strips call beside the one-peak call and the K = 4 call on the same frames (pairs/s);
 - the map (K = 1 peak per frame) in lag evaluations per second (G * P per frame) and in strip bytes read per second (8 B per
@@ -14,6 +15,9 @@ warm-up call, on buffers resident in HBM; kernel times are pal_profile's.
 - the zoom (pal_srp_zoom_dev, Z = 8, three levels, the first box one map cell on each side of the seed) alone at K = 1 and K = 2 on the
   peaks of the `grid`^3 map, and the `grid`^3 map alone against a (`grid` / 2)^3 map plus the zoom on the same strips: seconds, and the
   median and worst distance of the answer from the frame's source.
+- the direction map (pal_srp_doa_dev, K = 1) on a 72 x 36 and a 360 x 90 sphere and the direction zoom (pal_srp_doa_zoom_dev, Z = 8,
+  three levels, the first one cell of elevation) on each one's peaks, on the same strips: seconds, and the median and worst angle
+  between the answer and the source's direction from the array's centre, beside the same angle for the `grid`^3 map's peak.
 Frames: per frame one source inside the box, a common noise sequence delayed per microphone by the rounded path difference, plus
 independent noise of half its amplitude - host work, not timed."""
 import json
@@ -134,6 +138,48 @@ zoom_out = {
                              "zoomed_to_source_m": d_cz},
 }
 
+# the direction map (csrc/srp_doa.hip) on the same strips: two spheres and the zoom on each one's peaks, against the `grid`^3 map
+src_dir = sources / np.linalg.norm(sources, axis=1, keepdims=True)                   # the array's centre is the origin
+
+
+def angle_stats(u):
+    """Median and worst angle, in degrees, between the rows of u[frames][3] and the sources' directions from the array's centre."""
+    u = u / np.linalg.norm(u, axis=1, keepdims=True)
+    ang = np.degrees(np.arccos(np.clip(np.sum(u * src_dir, axis=1), -1.0, 1.0)))
+    return {"median": round(float(np.median(ang)), 3), "max": round(float(ang.max()), 3)}
+
+
+d_dzoom = eng.alloc(frames * _ffi.SRP_ZOOM.itemsize)
+doa_rows = {}
+for n_az, n_el in ((72, 36), (360, 90)):
+    az, el, wrap = srp.doa_axes(n_az, n_el)
+    t_d, k_d = best_of(lambda: (eng.srp_doa_dev(dev["strips"], frames, T, mics, fs, c, az, el, wrap, 0, 1, 1, dev["power"], dev["peaks"],
+                                                dev["summary"]), eng.synchronize()))
+    dpk = eng.download(np.zeros((frames, 1), dtype=_ffi.SRP_PEAK), dev["peaks"])
+    dsum = eng.download(np.zeros(frames, dtype=_ffi.SRP_FRAME), dev["summary"])
+    t_dz, k_dz = best_of(lambda: (eng.srp_doa_zoom_dev(dev["strips"], frames, T, mics, fs, c, dev["peaks"], 1, np.pi / n_el, ZOOM_Z, ZOOM_LEVELS,
+                                                       d_dzoom), eng.synchronize()))
+    dz = eng.download(np.zeros((frames, 1), dtype=_ffi.SRP_ZOOM), d_dzoom)
+    t_kd = k_d.get("k_srp_doa", {"ms": 0})["ms"] / 1e3
+    doa_rows[f"{n_az}x{n_el}"] = {
+        "cells": n_az * n_el, "cell_deg": round(180.0 / n_el, 3), "map_seconds_per_call": round(t_d, 6),
+        "map_kernels": {n: v for n, v in k_d.items() if n.startswith("k_srp") and v["launches"]},
+        "k_srp_doa_lag_evaluations_per_s": round(frames * n_az * n_el * P / t_kd, 1) if t_kd else None,
+        "clipped_terms": int(dsum["clipped"].sum()), "first_peak_to_source_deg": angle_stats(np.stack([dpk["x"][:, 0], dpk["y"][:, 0], dpk["z"][:, 0]], axis=1)),
+        "zoom_seconds_per_call": round(t_dz, 6), "zoom_kernels": {n: v for n, v in k_dz.items() if n.startswith("k_srp") and v["launches"]},
+        "zoom_clipped_terms": int(dz["clipped"].sum()), "zoom_levels_completed_min": int(dz["levels"].min()),
+        "zoomed_to_source_deg": angle_stats(np.stack([dz["x"][:, 0], dz["y"][:, 0], dz["z"][:, 0]], axis=1))}
+eng.free(d_dzoom)
+doa_out = {
+    "workload": {"frames": frames, "mics": mics_n, "pairs": P, "fs": fs, "half_width_T": T, "smoothing_W": W, "repeats": repeats,
+                 "array_radius_m": 0.5, "source_range_m": {"min": round(float(np.linalg.norm(sources, axis=1).min()), 3),
+                                                           "median": round(float(np.median(np.linalg.norm(sources, axis=1))), 3),
+                                                           "max": round(float(np.linalg.norm(sources, axis=1).max()), 3)},
+                 "zoom": {"Z": ZOOM_Z, "levels": ZOOM_LEVELS, "cells_per_seed": ZOOM_LEVELS * ZOOM_Z ** 2, "half0": "one cell of elevation"}},
+    "direction_maps": doa_rows,
+    "position_map": {"grid": list(count), "cells": G, "seconds_per_call": round(t_map, 6), "first_peak_to_source_deg": angle_stats(pos)},
+}
+
 # the specification on a grid small enough to time, against the device's map of that grid
 strips0 = eng.download(np.zeros((P, width)), dev["strips"])                           # frame 0
 t0 = time.perf_counter()
@@ -172,6 +218,10 @@ with open(os.path.join(ROOT, "profiles", "srp_bench.json"), "w") as fh:
 with open(os.path.join(ROOT, "profiles", "srp_zoom_bench.json"), "w") as fh:
     json.dump(zoom_out, fh, indent=1)
     fh.write("\n")
+with open(os.path.join(ROOT, "profiles", "srp_doa_bench.json"), "w") as fh:
+    json.dump(doa_out, fh, indent=1)
+    fh.write("\n")
 print(json.dumps(out))
 print(json.dumps(zoom_out))
+print(json.dumps(doa_out))
 eng.close()

@@ -158,6 +158,8 @@ SIGNATURES = {
     "pal_simulate_multipath": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pal_fractional_delay": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p]),
+    "pal_steer_sum": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pal_steer_sum_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pal_normalize_compress": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "pal_filtfilt": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                C.c_void_p]),

@@ -1,0 +1,281 @@
+// beamform.hip - delay-and-sum beamformer: frames[B][M][L] steered at S points per frame (specification: beamform.py).
+//
+//   out[b,s] = ifft(sum_m w[b,s,m] X[b,m] exp(-j 2 pi f d[b,s,m])).real[:L] * fade_window(L),   X = fft(frames[b,m], 2L)
+//
+// the transpose of sim.hip's multipath synthesis (one base, many paths): many microphones, one output row.  Per slice of whole
+// frames: the forward spectra of the slice's rows (Engine::forward_spectra at the plan of fractional_delay), k_steer_sum forms the
+// S beam spectra of every frame while it reads each microphone spectrum once per tile of up to 8 beams, and the beams go through the
+// exact-length inverse DFT(2L) two rows per complex transform (BeamLoader -> launch_cols_fwd / launch_rows / launch_cols_inv ->
+// SimStorer: fade window, exponent put back).  Built with -ffp-contract=off: the operation order below is what runs.
+#include <cmath>
+
+#include "conv_kernels.h"
+#include "reduce.h"
+#include "sim_rows.h"
+
+namespace pal {
+
+namespace {
+
+constexpr int kSteerBins = 256;    // bins per workgroup: one per lane
+constexpr int kSteerMics = 64;     // microphones per LDS tile of the frame's delays and weights
+constexpr int kSteerMaxTile = 8;   // beams per pass: their accumulators live in registers
+
+// a delay or weight that is not finite, or a delay that leaves nothing of the row (the circular transform would wrap)
+__global__ __launch_bounds__(256) void k_steer_check(const double* __restrict__ delays, const double* __restrict__ weights, size_t n,
+                                                     double fs, double L, int* __restrict__ status) {
+  const size_t i = size_t(blockIdx.x) * 256 + threadIdx.x;
+  bool bad = false;
+  if (i < n) {
+    const double d = delays[i], w = weights[i];
+    bad = !(d - d == 0.0) || !(w - w == 0.0) || fabs(d) * fs > L;
+  }
+  if (__syncthreads_or(bad ? 1 : 0) && threadIdx.x == 0) atomicOr(status + kStInput, kStInputBadSteer);
+}
+
+// Y[f,s,k] = sum_m w[f,s,m] X[f,m,k] exp(j theta), theta = (-6.283185307179586 f_k) d[f,s,m], m = 0 .. M-1 in this order, for the
+// beams s0 .. s0 + ns - 1 (ns <= ST) of every frame of the slice; f_k = k val, and -N val at the Nyquist bin k = N
+// (SimLoader::term's operation order).  One lane owns one bin, a workgroup 256 consecutive bins of one frame: every step of the
+// loop over m is one coalesced 16-byte load per lane (the next one is issued before this one is used) that serves all ns beams.
+// The frame's delays and weights are uniform over the workgroup and come through LDS, 64 microphones at a time.
+// Exponents: a frame row's is in its flag word (k_row_nonzero); a beam's is e = ilogb(sum_m |w_m| 2^e_m) over the live rows, Y leaves
+// times 2^-e and SimStorer multiplies 2^e back, so a beam never sees the amplitude of the beam it shares a transform with.  A beam
+// without a live weighted row (all weights zero, or only silent rows) is marked dead: zero spectrum here, zero row in k_steer_silence.
+template <int ST>
+__global__ __launch_bounds__(256) void k_steer_sum(const cd* __restrict__ X, const int* __restrict__ flags, const double* __restrict__ delays,
+                                                   const double* __restrict__ weights, int M, int N, int S, int s0, int ns, double val,
+                                                   cd* __restrict__ Y, int* __restrict__ beam_exp, int* __restrict__ beam_live) {
+  __shared__ double sd[ST][kSteerMics], sw[ST][kSteerMics], samp[kSteerMics];
+  const int H = N + 1, f = blockIdx.y, tid = threadIdx.x;
+  const int k = blockIdx.x * kSteerBins + tid;
+  const bool in_row = k < H;
+  const int kk = in_row ? k : H - 1;                          // lanes past the row compute bin N again and store nothing
+  const double fk = kk == N ? -double(N) * val : double(kk) * val;   // fftfreq: bin N carries -fs/2
+  const double a = -6.283185307179586 * fk;
+  const cd* x = X + size_t(f) * size_t(M) * size_t(H) + size_t(kk);
+  double ax[ST], ay[ST], top[ST];
+#pragma unroll
+  for (int q = 0; q < ST; ++q) ax[q] = ay[q] = top[q] = 0.0;
+  for (int m0 = 0; m0 < M; m0 += kSteerMics) {
+    const int mt = M - m0 < kSteerMics ? M - m0 : kSteerMics;
+    __syncthreads();                                          // the previous tile has been read
+    for (int i = tid; i < ST * kSteerMics; i += kSteerBins) {
+      const int q = i / kSteerMics, m = i % kSteerMics;
+      const bool on = q < ns && m < mt;
+      const size_t at = (size_t(f) * size_t(S) + size_t(s0 + (on ? q : 0))) * size_t(M) + size_t(m0 + (on ? m : 0));
+      sd[q][m] = on ? delays[at] : 0.0;
+      sw[q][m] = on ? weights[at] : 0.0;
+    }
+    if (tid < kSteerMics) {
+      const int fl = tid < mt ? flags[size_t(f) * size_t(M) + size_t(m0 + tid)] : 0;
+      samp[tid] = fl ? ldexp(1.0, flag_exponent(fl)) : 0.0;   // 2^e_m of a live row
+    }
+    __syncthreads();
+    cd nxt = x[size_t(m0) * size_t(H)];
+    for (int m = 0; m < mt; ++m) {
+      const cd xv = nxt;
+      if (m + 1 < mt) nxt = x[size_t(m0 + m + 1) * size_t(H)];   // (two and three loads ahead measured no faster: DESIGN 6j)
+      const double amp = samp[m];
+#pragma unroll
+      for (int q = 0; q < ST; ++q) {
+        if (q < ns) {                                         // (uniform)
+          double s, c;
+          sincos(a * sd[q][m], &s, &c);
+          const cd t = cmul(xv, mk(c, s));
+          const double w = sw[q][m];
+          ax[q] = ax[q] + w * t.x;
+          ay[q] = ay[q] + w * t.y;
+          top[q] = top[q] + fabs(w) * amp;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < ST; ++q) {
+    if (q < ns) {
+      const bool live = top[q] > 0.0;
+      const int e = row_exponent(top[q]);
+      const size_t row = size_t(f) * size_t(S) + size_t(s0 + q);
+      if (in_row) Y[row * size_t(H) + size_t(k)] = live ? mk(ldexp(ax[q], -e), ldexp(ay[q], -e)) : mk(0, 0);
+      if (blockIdx.x == 0 && tid == 0) {
+        beam_exp[row] = e;
+        beam_live[row] = live ? 1 : 0;
+      }
+    }
+  }
+}
+
+// the half spectra of two beams -> one complex transform of 2N points (SimLoader::operator()'s mirror and Nyquist rules)
+struct BeamLoader {
+  static constexpr const char* kName = "BeamLoader";
+  const cd* Y;            // beam spectra [rows][N + 1], each times 2^-e of its beam
+  int rows, N, row0;      // row0: first row of this launch group
+  const cd* w;
+  __device__ cd term(int r, unsigned kk, bool nyquist, bool mirror) const {
+    r += row0;
+    if (r >= rows) return mk(0, 0);
+    cd z = Y[size_t(r) * size_t(N + 1) + kk];
+    if (nyquist) z.y = 0;                                   // only the real part of bin N survives .real
+    if (mirror) z.y = -z.y;
+    return z;
+  }
+  __device__ cd operator()(int g, unsigned j) const {
+    const unsigned n = 2u * unsigned(N);
+    if (j >= n) return mk(0, 0);
+    const bool mirror = j > unsigned(N), nyq = j == unsigned(N);
+    const unsigned kk = mirror ? n - j : j;
+    const cd z1 = term(2 * g, kk, nyq, mirror);
+    const cd z2 = term(2 * g + 1, kk, nyq, mirror);
+    return cmul(mk(z1.x - z2.y, z1.y + z2.x), w[j]);
+  }
+};
+
+// a dead beam (k_steer_sum) shares its transform with a live one and carries that one's rounding noise: written as zeros
+__global__ __launch_bounds__(256) void k_steer_silence(double* __restrict__ out, int L, const int* __restrict__ beam_live) {
+  if (beam_live[blockIdx.x]) return;                          // (uniform over the workgroup)
+  double* y = out + size_t(blockIdx.x) * size_t(L);
+  for (int i = threadIdx.x; i < L; i += 256) y[i] = 0.0;
+}
+
+template <int ST>
+void launch_steer_sum(dim3 grid, hipStream_t on, const cd* X, const int* flags, const double* delays, const double* weights, int M, int N,
+                      int S, int s0, int ns, double val, cd* Y, int* beam_exp, int* beam_live) {
+  k_steer_sum<ST><<<grid, dim3(kSteerBins), 0, on>>>(X, flags, delays, weights, M, N, S, s0, ns, val, Y, beam_exp, beam_live);
+}
+
+}  // namespace
+
+int Engine::steer_check(int B, int M, int L, double fs, int S) {
+  if (B < 1 || M < 1 || S < 1) return fail(PAL_ERR_INVALID, "need B >= 1, M >= 1, S >= 1 (got %d, %d, %d)", B, M, S);
+  if (!(fs > 0) || !std::isfinite(fs)) return fail(PAL_ERR_INVALID, "fs must be positive and finite");
+  if (L < 100) return fail(PAL_ERR_INVALID, "steering needs at least 100 samples (fade slice of signal_processing.py:75-78)");
+  if (L > (1 << 19)) return fail(PAL_ERR_UNSUPPORTED, "frame length %d exceeds 2^19", L);
+  if (int64_t(B) * M > INT32_MAX / 2 || int64_t(B) * S > INT32_MAX / 2) return fail(PAL_ERR_UNSUPPORTED, "too many rows");
+  return PAL_OK;
+}
+
+int Engine::steer_sum_dev(const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_weights, int S,
+                          double* d_out) {
+  Engine* e = this;
+  if (!d_frames || !d_delays || !d_weights || !d_out) return fail(PAL_ERR_INVALID, "NULL buffer");
+  PAL_TRY(steer_check(B, M, L, fs, S));
+  Plan* pl = nullptr;
+  PAL_TRY(get_plan(2 * L, L, L, &pl));
+  if (pfa_forward_applies(*pl, L)) return fail(PAL_ERR_INTERNAL, "packed forward transform on a steering plan");
+  int* status = nullptr;
+  PAL_TRY(status_words(&status));
+  const size_t ntab = size_t(B) * size_t(S) * size_t(M);
+  k_steer_check<<<dim3(unsigned((ntab + 255) / 256)), dim3(256), 0, stream>>>(d_delays, d_weights, ntab, fs, double(L), status);
+  PAL_TRY(check(hipGetLastError(), "k_steer_check"));
+  // slices of whole frames: the spectra of one slice stay near 1 GiB (the bound of the SRP strips' slices), at most 32768 frames
+  // (the grid's second dimension)
+  const size_t H = size_t(pl->H);
+  size_t per = (size_t(1) << 30) / (size_t(M) * H * sizeof(cd));
+  if (beam_slice > 0) per = size_t(beam_slice);
+  per = per < 1 ? 1 : (per > 32768 ? 32768 : per);
+  const int F0 = int(per > size_t(B) ? size_t(B) : per);
+  Carve cv;
+  const size_t off_x = cv.take(size_t(F0) * M * H * sizeof(cd));
+  const size_t off_y = cv.take(size_t(F0) * S * H * sizeof(cd));
+  const size_t off_flags = cv.take(size_t(F0) * M * sizeof(int));
+  const size_t off_exp = cv.take(size_t(F0) * S * sizeof(int));
+  const size_t off_live = cv.take(size_t(F0) * S * sizeof(int));
+  char* blk = nullptr;
+  PAL_TRY(scratch(kWsBeam, cv.off, &blk));
+  cd* X = reinterpret_cast<cd*>(blk + off_x);
+  cd* Y = reinterpret_cast<cd*>(blk + off_y);
+  int* flags = reinterpret_cast<int*>(blk + off_flags);
+  int* beam_exp = reinterpret_cast<int*>(blk + off_exp);
+  int* beam_live = reinterpret_cast<int*>(blk + off_live);
+  const Conv& c = pl->inv;
+  const int fl = int(0.01 * double(L));
+  const double d = 1.0 / fs;
+  const double val = 1.0 / (double(2 * L) * d);
+  for (int f0 = 0; f0 < B; f0 += F0) {
+    const int F = B - f0 < F0 ? B - f0 : F0;
+    {
+      ProfScope ps(e, "steer_forward_spectra");
+      PAL_TRY(forward_spectra(*pl, d_frames + size_t(f0) * M * L, size_t(L), F * M, L, X, flags));
+    }
+    const double* dl = d_delays + size_t(f0) * S * M;
+    const double* wt = d_weights + size_t(f0) * S * M;
+    {
+      ProfScope ps(e, "k_steer_sum");
+      const dim3 grid(unsigned((H + kSteerBins - 1) / kSteerBins), unsigned(F));
+      for (int s0 = 0; s0 < S; s0 += kSteerMaxTile) {
+        const int ns = S - s0 < kSteerMaxTile ? S - s0 : kSteerMaxTile;
+        if (ns == 1) launch_steer_sum<1>(grid, stream, X, flags, dl, wt, M, L, S, s0, ns, val, Y, beam_exp, beam_live);
+        else if (ns == 2) launch_steer_sum<2>(grid, stream, X, flags, dl, wt, M, L, S, s0, ns, val, Y, beam_exp, beam_live);
+        else if (ns <= 4) launch_steer_sum<4>(grid, stream, X, flags, dl, wt, M, L, S, s0, ns, val, Y, beam_exp, beam_live);
+        else launch_steer_sum<8>(grid, stream, X, flags, dl, wt, M, L, S, s0, ns, val, Y, beam_exp, beam_live);
+      }
+    }
+    PAL_TRY(check(hipGetLastError(), "k_steer_sum"));
+    const int rows = F * S;
+    double* out = d_out + size_t(f0) * S * L;
+    cd* W = nullptr;
+    PAL_TRY(scratch(kWsWork, size_t(chunk) * c.M() * sizeof(cd), &W));
+    {
+      ProfScope ps(e, "steer_inverse");
+      const int ntr = (rows + 1) / 2;
+      for (int t0 = 0; t0 < ntr; t0 += chunk) {
+        const int G = ntr - t0 < chunk ? ntr - t0 : chunk;
+        const int r0 = 2 * t0;
+        BeamLoader ld{Y, rows, L, r0, pl->w};
+        SimStorer st{out, size_t(L), rows, L, L, fl, r0, fl > 1 ? 1.0 / double(fl - 1) : 0.0, fl > 1 ? -1.0 / double(fl - 1) : 0.0,
+                     pl->w, beam_exp, 1};
+        PAL_TRY(launch_cols_fwd(e, c, G, ld, W));
+        PAL_TRY(launch_rows(e, c, G, W, true, 1.0));
+        PAL_TRY(launch_cols_inv(e, c, G, W, st));
+      }
+      k_steer_silence<<<dim3(unsigned(rows)), dim3(256), 0, stream>>>(out, L, beam_live);
+      PAL_TRY(check(hipGetLastError(), "k_steer_silence"));
+    }
+  }
+  return PAL_OK;
+}
+
+}  // namespace pal
+
+using namespace pal;
+
+#define ENGINE(h)                                   \
+  if (!(h)) return PAL_ERR_INVALID;                 \
+  Engine* e = reinterpret_cast<Engine*>(h);         \
+  if (hipSetDevice(e->device) != hipSuccess) return e->fail(PAL_ERR_HIP, "hipSetDevice(%d) failed", e->device)
+
+#define UP(dst, src, bytes) PAL_TRY(e->check(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, e->stream), "upload"))
+#define DOWN(dst, src, bytes) PAL_TRY(e->check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream), "download"))
+
+extern "C" {
+
+int pal_steer_sum_dev(pal_handle h, const double* d_frames, int B, int M, int L, double fs, const double* d_delays,
+                      const double* d_weights, int S, double* d_out) {
+  ENGINE(h);
+  return e->steer_sum_dev(d_frames, B, M, L, fs, d_delays, d_weights, S, d_out);
+}
+
+int pal_steer_sum(pal_handle h, const double* frames, int B, int M, int L, double fs, const double* delays, const double* weights, int S,
+                  double* out) {
+  ENGINE(h);
+  if (!frames || !delays || !weights || !out) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  PAL_TRY(e->steer_check(B, M, L, fs, S));
+  const size_t nin = size_t(B) * M * L, ntab = size_t(B) * S * M, nout = size_t(B) * S * L;
+  for (size_t i = 0; i < ntab; ++i) {                       // (the device checks the same: refused here before anything is uploaded)
+    if (!std::isfinite(delays[i]) || !std::isfinite(weights[i])) return e->fail(PAL_ERR_INVALID, "a steering delay or weight is not finite");
+    if (std::fabs(delays[i]) * fs > double(L)) return e->fail(PAL_ERR_INVALID, "a steering delay lies beyond the frame (|delay| fs > %d)", L);
+  }
+  double *dx = nullptr, *dt = nullptr, *dout = nullptr;
+  PAL_TRY(e->scratch(kWsStageIn, nin * sizeof(double), &dx));
+  PAL_TRY(e->scratch(kWsStageTable, 2 * ntab * sizeof(double), &dt));
+  PAL_TRY(e->scratch(kWsStageOut, nout * sizeof(double), &dout));
+  UP(dx, frames, nin * sizeof(double));
+  UP(dt, delays, ntab * sizeof(double));
+  UP(dt + ntab, weights, ntab * sizeof(double));
+  PAL_TRY(e->check(hipStreamSynchronize(e->stream), "upload sync"));
+  PAL_TRY(e->steer_sum_dev(dx, B, M, L, fs, dt, dt + ntab, S, dout));
+  DOWN(out, dout, nout * sizeof(double));
+  return pal_synchronize(h);
+}
+
+}  // extern "C"

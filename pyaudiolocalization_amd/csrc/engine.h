@@ -93,7 +93,8 @@ enum Ws : int {
   kWsConsensus = 29,   // the consensus (consensus.hip): frame lengths, candidate cubes, chosen-lag matrices, three selections, two vote tables
   kWsCandK = 30, kWsCandH = 31,   // the selected peaks of a launch group per stream slot (PAL_MAX_PEAKS indices / heights per row), compacted into a CandOut
   kWsSrp = 32,         // the SRP map (srp.hip): a frame slice's correlation rows and one-peak table, microphones, clip counters, peak marks, the map when the caller takes none
-  kWsCount = 33
+  kWsBeam = 33,        // the delay-and-sum beamformer (beamform.hip): a frame slice's spectra and row flags, its beam spectra, exponents and live marks
+  kWsCount = 34
 };
 constexpr Ws peak_scratch_slot(int slot) { return slot == 0 ? kWsPeaks0 : (slot == 1 ? kWsPeaks1 : kWsPeaks2); }
 constexpr Ws fin_scratch_slot(int slot) { return Ws(kWsFin0 + slot); }
@@ -274,6 +275,12 @@ struct Engine {
   int srp_doa_zoom_check(int B, int M, int T, const double* mics, double fs, double c, int K, double half0, int Z, int levels);
   int srp_doa_zoom_dev(const double* d_strips, int B, int M, int T, const double* mics, double fs, double c, const double* d_pair_weights,
                        const pal_srp_peak* d_seeds, int K, double half0, int Z, int levels, pal_srp_zoom_record* d_out);
+  // beamform.hip: delay-and-sum beams of frames[B][M][L] at delays / weights[B][S][M] -> out[B][S][L] (every pointer in HBM); asynchronous,
+  // a non-finite sample or a refused table entry is reported by pal_synchronize (kStInputNonFinite, kStInputBadSteer)
+  int steer_check(int B, int M, int L, double fs, int S);
+  int steer_sum_dev(const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_weights, int S,
+                    double* d_out);
+  int beam_slice = 0;              // PAL_BEAM_SLICE=<frames>: frames per slice of steer_sum_dev (0: as many as keep the slice's spectra near 1 GiB)
   int32_t* solve_idx = nullptr;    // device table pair -> i | j << 16 of the last microphone count
   int solve_idx_M = 0;
   // resample.hip: the right wing of the interpolation filter as pal_resample_set_filter received it, and the ratio whose scaled

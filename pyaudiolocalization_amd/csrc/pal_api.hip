@@ -131,6 +131,8 @@ static int check_status(Engine* e) {
     if (st[kStInput] & kStInputBadLag) return e->fail(PAL_ERR_INVALID, "a record of the TDOA table has k_sel outside 0..2 length - 2: the closure results of this call are not valid");
     if (st[kStInput] & kStInputBadCandidate)
       return e->fail(PAL_ERR_INVALID, "a candidate outside 0..2 length - 2, an absent candidate 0 or a gap in a pair's candidates: the consensus results of this call are not valid");
+    if (st[kStInput] & kStInputBadSteer)
+      return e->fail(PAL_ERR_INVALID, "a steering delay or weight that is not finite, or a delay beyond the frame (|delay| fs > length): the beams of this call are not valid");
     return e->fail(PAL_ERR_INVALID, "non-finite sample (NaN or infinity) in a frame: the pair packed with that microphone's "
                                     "pairs would be affected too, the table of this call is not valid");
   }
@@ -372,6 +374,8 @@ int pal_create(int device, pal_handle* out) {
   if (env) e->fin_giveup = atoi(env) != 0 ? 1 : 0;
   env = getenv("PAL_MAX_PLANS");
   if (env && atoi(env) >= 2) e->max_plans = atoi(env);
+  env = getenv("PAL_BEAM_SLICE");
+  if (env && atoi(env) >= 1) e->beam_slice = atoi(env);
   *out = reinterpret_cast<pal_handle>(e);
   return PAL_OK;
 }

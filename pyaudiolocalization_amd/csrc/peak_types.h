@@ -21,9 +21,10 @@ enum StatusWord : int {
   kStatusWords = 16
 };
 constexpr int kStWhyCount = 8;
-enum StatusInputBit : int { kStInputNonFinite = 1, kStInputBadRow = 2, kStInputBadLag = 4, kStInputBadCandidate = 8 };   // a NaN or an infinity in a frame; a pair list references
+enum StatusInputBit : int { kStInputNonFinite = 1, kStInputBadRow = 2, kStInputBadLag = 4, kStInputBadCandidate = 8,     // a NaN or an infinity in a frame; a pair list references
                                                                                                // a row outside the frame batch; a record of a TDOA table whose k_sel lies outside 0..2L-2
                                                                                                // (closure.hip); a candidate outside 0..2L-2, an absent candidate 0 or a gap (consensus.hip)
+                            kStInputBadSteer = 16 };                                           // a steering delay or weight that is not finite, or |delay| fs > L (beamform.hip)
 
 struct RowPre {                          // pivot launch -> the other two
   double k0, ka;                         // ~ mean(x), ~ mean(|x|): shifts of the one-pass sums

@@ -729,6 +729,40 @@ class Engine:
                                                    out.ctypes.data))
         return out[0] if one else out
 
+    def steer(self, frames, fs, delays, weights=None) -> np.ndarray:
+        """Delay-and-sum beams: frames[B][M][L], delays[B][S][M] (seconds) and weights[B][S][M] (None: 1/M) -> out[B][S][L]
+        (rule: beamform.steer).  frames[M][L] with delays[S][M] gives out[S][L]."""
+        x, d = f64(frames), f64(delays)
+        one = x.ndim == 2 and d.ndim == 2
+        if one:
+            x, d = x[None], d[None]
+        if x.ndim != 3 or d.ndim != 3 or d.shape[0] != x.shape[0] or d.shape[2] != x.shape[1]:
+            raise ValueError("frames must be [B][M][L] with delays[B][S][M] (or [M][L] with [S][M])")
+        b, m, length = x.shape
+        s = d.shape[1]
+        if weights is None:
+            w = np.full(d.shape, 1.0 / m if m else 0.0)
+        else:
+            w = f64(weights)
+            if one and w.ndim == 2:
+                w = w[None]
+            if w.shape != d.shape:
+                raise ValueError("weights must have the shape of delays")
+        if m < 1 or s < 1 or b < 1:
+            raise ValueError("need at least one frame, one microphone and one steering point")
+        if length < 100:
+            raise ValueError("steering needs at least 100 samples (the fade window of fractional_delay)")
+        out = np.empty((b, s, length))
+        self._check(self._lib.pal_steer_sum(self._h, x.ctypes.data, b, m, length, float(fs), d.ctypes.data, w.ctypes.data, s,
+                                            out.ctypes.data))
+        return out[0] if one else out
+
+    def steer_dev(self, d_frames: int, b: int, m: int, length: int, fs: float, d_delays: int, d_weights: int, s: int, d_out: int) -> None:
+        """Engine.steer on buffers in HBM: d_frames[b][m][length], d_delays / d_weights[b][s][m] -> d_out[b][s][length]; asynchronous,
+        refused table entries and non-finite samples surface in synchronize()."""
+        self._check(self._lib.pal_steer_sum_dev(self._h, C.c_void_p(d_frames), int(b), int(m), int(length), float(fs), C.c_void_p(d_delays),
+                                                C.c_void_p(d_weights), int(s), C.c_void_p(d_out)))
+
     def normalize_compress(self, rows, normalize_only=False, threshold=0.8, epsilon=1e-8) -> np.ndarray:
         x = f64(rows)
         one = x.ndim == 1

@@ -285,6 +285,47 @@ def srp_directions_device(frames, mic_positions, fs, c, n_az=72, n_el=36, W=2, K
     return (peaks[0], zoomed[0]) if one else (peaks, zoomed)
 
 
+def beamform_device(frames, mic_positions, fs, c, points=None, directions=None, weights=None, calib_delays=None, engine=None):
+    """frames[B][M][L] (or [M][L]) -> out[B][S][L] (or [S][L]): every frame's delay-and-sum beams at ``points`` or ``directions``
+    (exactly one of them; Engine.steer, rule: beamform.py).  Either is [B][S][3], or [S][3] for every frame, or an array of
+    _ffi.SRP_PEAK / _ffi.SRP_ZOOM records, so the peaks or the zoom results of srp_positions_device and srp_directions_device go in as
+    they are: steering at peaks 0 and 1 is what separates two sources.  An absent record or a point with a non-finite coordinate
+    gives a row of zeros.  ``weights``: [B][S][M] (or what broadcasts to it), by default 1/M.  ``calib_delays``: the per-microphone
+    calibration delays localize_sound_source corrects the pair delays with."""
+    from . import beamform
+    if (points is None) == (directions is None):
+        raise ValueError("give exactly one of points and directions")
+    eng = engine or default_engine()
+    x = np.ascontiguousarray(frames, dtype=np.float64)
+    one = x.ndim == 2
+    if one:
+        x = x[None]
+    if x.ndim != 3:
+        raise ValueError("frames must be [M][L] or [B][M][L]")
+    mics = np.ascontiguousarray(mic_positions, dtype=np.float64)
+    if mics.shape != (x.shape[1], 3):
+        raise ValueError("one microphone position per row of a frame")
+    where = np.asarray(points if points is not None else directions)
+    if where.dtype.names:
+        where = beamform.records_to_points(where)
+    else:
+        where = np.asarray(where, dtype=np.float64)
+    if one and where.ndim == 3 and where.shape[0] == 1:
+        where = where[0]
+    if where.ndim == 2:
+        where = np.broadcast_to(where[None], (x.shape[0],) + where.shape)
+    if where.ndim != 3 or where.shape[0] != x.shape[0] or where.shape[2] != 3:
+        raise ValueError("points / directions must be [B][S][3], [S][3] or SRP records [B][S]")
+    to_delays = beamform.point_delays if points is not None else beamform.direction_delays
+    delays, valid = to_delays(where, mics, c, calib_delays)
+    if weights is None:
+        w = beamform.uniform_weights(valid, x.shape[1])
+    else:
+        w = np.where(valid[..., None], np.broadcast_to(np.asarray(weights, dtype=np.float64), delays.shape), 0.0)
+    out = eng.steer(x, fs, delays, w)
+    return out[0] if one else out
+
+
 def localize_sound_source(config, calibration_data=None, audio_files=None, use_simulation=True, show_plots=True):
     fs = config["fs"]
     duration = config["duration"]

@@ -92,7 +92,7 @@ enum Ws : int {
   kWsFinStrip0 = 26, kWsFinStrip1 = 27, kWsFinStrip2 = 28,   // its SNR strips (pair_route.h fin_strip) per stream slot, see fin_strip_slot
   kWsConsensus = 29,   // the consensus (consensus.hip): frame lengths, candidate cubes, chosen-lag matrices, three selections, two vote tables
   kWsCandK = 30, kWsCandH = 31,   // the selected peaks of a launch group per stream slot (PAL_MAX_PEAKS indices / heights per row), compacted into a CandOut
-  kWsSrp = 32,         // the SRP map (srp.hip): a frame slice's correlation rows and one-peak table, microphones, clip counters, peak marks, the map when the caller takes none
+  kWsSrp = 32,         // SRP (srp.hip): a frame slice's correlation rows and one-peak table (the strips call); microphones, direction tables, clip counters, peak marks, the map when the caller takes none (SrpCarve: every other call)
   kWsBeam = 33,        // the delay-and-sum beamformer (beamform.hip): a frame slice's spectra and row flags, its beam spectra, exponents and live marks
   kWsCount = 34
 };
@@ -250,7 +250,8 @@ struct Engine {
                          pal_consensus_frame* d_summary);
   int consensus_check(int B, int M, int K, const int32_t* lengths, int32_t tol, int32_t rounds);
   // srp.hip: lag strips of stored rows, the steered-response power map and its peaks (every pointer but `mics` and `grid` in HBM, each
-  // output or nullptr); asynchronous.  The *_check functions hold the argument checks that the host and the _dev forms share.
+  // output or nullptr); asynchronous.  The *_check functions hold the argument checks that the host and the _dev forms share; the maps'
+  // and the zooms' go through one common check of B, M, T, mics, fs, c, K, R and the outputs, the cheap checks first.
   int srp_strips_check(int B, int M, int L, int T, int W);
   int srp_strips_rows(const double* d_rows, int64_t nrows, int L, int T, int W, double* d_strips);   // k_srp_strips on rows[nrows][2L-1]
   int srp_map_check(int B, int M, int T, const double* mics, double fs, double c, const pal_srp_grid* grid, int K, int R, bool any_output,
@@ -263,7 +264,8 @@ struct Engine {
   int srp_zoom_check(int B, int M, int T, const double* mics, double fs, double c, int K, const double* half0, int Z, int levels);
   int srp_zoom_dev(const double* d_strips, int B, int M, int T, const double* mics, double fs, double c, const double* d_pair_weights,
                    const pal_srp_peak* d_seeds, int K, const double* half0, int Z, int levels, pal_srp_zoom_record* d_out);
-  // the direction map, its peaks and its zoom (k_srp_doa, k_srp_doa_peaks, k_srp_doa_zoom): `mics`, `grid`, `az` and `el` are host memory
+  // the direction map, its peaks and its zoom (k_srp_doa, k_srp_doa_peaks, k_srp_doa_zoom, also in srp.hip): `mics`, `grid`, `az` and
+  // `el` are host memory
   int srp_doa_check(int B, int M, int T, const double* mics, double fs, double c, const pal_srp_doa_grid* grid, const double* az,
                     const double* el, int K, int R, bool any_output, bool peaks_out);
   int srp_doa_dev(const double* d_strips, int B, int M, int T, const double* mics, double fs, double c, const pal_srp_doa_grid* grid,

@@ -746,7 +746,7 @@ int pal_tdoa_consensus(pal_handle h, const pal_pair_record* tables, const int32_
   return pal_synchronize(h);
 }
 
-// ---- steered-response power map (srp.hip): lag strips of all pairs, the map over a grid, the map's peaks ----
+// ---- steered-response power (srp.hip): lag strips of all pairs; the map over a box, its peaks and its zoom; the direction map ----
 int pal_gcc_phat_all_pairs_strips_dev(pal_handle h, const double* d_frames, int B, int M, int L, const pal_phat_params* prm, int T, int W,
                                       pal_pair_record* d_table, double* d_strips) {
   ENGINE(h);
@@ -774,21 +774,16 @@ int pal_gcc_phat_all_pairs_strips(pal_handle h, const double* frames, int B, int
   return pal_synchronize(h);
 }
 
-int pal_srp_map_dev(pal_handle h, const double* d_strips, int B, int M, int T, const double* mics, double fs, double c,
-                    const pal_srp_grid* grid, const double* d_pair_weights, int K, int R, double* d_power, pal_srp_peak* d_peaks,
-                    pal_srp_frame* d_summary) {
-  ENGINE(h);
-  return e->srp_map_dev(d_strips, B, M, T, mics, fs, c, grid, d_pair_weights, K, R, d_power, d_peaks, d_summary);
-}
+// The staged host forms of the map, the peaks and the zoom, each written once for the box and the direction grid: behind the caller's
+// check they take the grid's cell count G and `dev`, the engine's device call on the staged buffers.
+extern "C++" {
 
-int pal_srp_map(pal_handle h, const double* strips, int B, int M, int T, const double* mics, double fs, double c, const pal_srp_grid* grid,
-                const double* pair_weights, int K, int R, double* power, pal_srp_peak* peaks, pal_srp_frame* summary) {
-  ENGINE(h);
-  PAL_TRY(e->srp_map_check(B, M, T, mics, fs, c, grid, K, R, power || peaks || summary, peaks != nullptr));
+// inputs [strips | pair_weights] and outputs [power | peaks | summary], one block each; dev(d_strips, d_weights, d_power, d_peaks, d_summary)
+template <class DEV>
+static int srp_map_staged(pal_handle h, Engine* e, const double* strips, int B, int M, int T, const double* pair_weights, int K, size_t G,
+                          double* power, pal_srp_peak* peaks, pal_srp_frame* summary, DEV dev) {
   if (!strips) return e->fail(PAL_ERR_INVALID, "NULL buffer");
-  const size_t P = size_t(M) * size_t(M - 1) / 2, np = size_t(B) * P;
-  const size_t G = size_t(grid->count[0]) * size_t(grid->count[1]) * size_t(grid->count[2]);
-  // staged inputs [strips | pair_weights] and outputs [power | peaks | summary], one block each
+  const size_t np = size_t(B) * (size_t(M) * size_t(M - 1) / 2);
   Carve ci, co;
   const size_t sbytes = np * size_t(2 * T + 1) * sizeof(double);
   const size_t o_st = ci.take(sbytes), o_w = ci.take(pair_weights ? np * sizeof(double) : 0);
@@ -802,12 +797,72 @@ int pal_srp_map(pal_handle h, const double* strips, int B, int M, int T, const d
   double* dpw = power ? reinterpret_cast<double*>(out + o_pw) : nullptr;
   pal_srp_peak* dpk = peaks ? reinterpret_cast<pal_srp_peak*>(out + o_pk) : nullptr;
   pal_srp_frame* dsum = summary ? reinterpret_cast<pal_srp_frame*>(out + o_sum) : nullptr;
-  PAL_TRY(e->srp_map_dev(reinterpret_cast<const double*>(in + o_st), B, M, T, mics, fs, c, grid,
-                         pair_weights ? reinterpret_cast<const double*>(in + o_w) : nullptr, K, R, dpw, dpk, dsum));
+  PAL_TRY(dev(reinterpret_cast<const double*>(in + o_st), pair_weights ? reinterpret_cast<const double*>(in + o_w) : nullptr, dpw, dpk, dsum));
   if (power) PAL_TRY(e->check(hipMemcpyAsync(power, dpw, size_t(B) * G * sizeof(double), hipMemcpyDeviceToHost, e->stream), "map download"));
   if (peaks) PAL_TRY(e->check(hipMemcpyAsync(peaks, dpk, size_t(B) * size_t(K) * sizeof(pal_srp_peak), hipMemcpyDeviceToHost, e->stream), "peaks download"));
   if (summary) PAL_TRY(e->check(hipMemcpyAsync(summary, dsum, size_t(B) * sizeof(pal_srp_frame), hipMemcpyDeviceToHost, e->stream), "summary download"));
   return pal_synchronize(h);
+}
+
+// the map in, [peaks | summary] out; dev(d_power, d_peaks, d_summary)
+template <class DEV>
+static int srp_peaks_staged(pal_handle h, Engine* e, const double* power, int B, int K, size_t G, pal_srp_peak* peaks, pal_srp_frame* summary,
+                            DEV dev) {
+  if (!power || !peaks) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  Carve co;
+  const size_t o_pk = co.take(size_t(B) * size_t(K) * sizeof(pal_srp_peak)), o_sum = co.take(summary ? size_t(B) * sizeof(pal_srp_frame) : 0);
+  void* in = nullptr;
+  char* out = nullptr;
+  PAL_TRY(e->scratch(kWsStageIn, size_t(B) * G * sizeof(double), &in));
+  PAL_TRY(e->scratch(kWsStageOut, co.off, &out));
+  PAL_TRY(e->check(hipMemcpyAsync(in, power, size_t(B) * G * sizeof(double), hipMemcpyHostToDevice, e->stream), "map upload"));
+  pal_srp_peak* dpk = reinterpret_cast<pal_srp_peak*>(out + o_pk);
+  pal_srp_frame* dsum = summary ? reinterpret_cast<pal_srp_frame*>(out + o_sum) : nullptr;
+  PAL_TRY(dev(static_cast<const double*>(in), dpk, dsum));
+  PAL_TRY(e->check(hipMemcpyAsync(peaks, dpk, size_t(B) * size_t(K) * sizeof(pal_srp_peak), hipMemcpyDeviceToHost, e->stream), "peaks download"));
+  if (summary) PAL_TRY(e->check(hipMemcpyAsync(summary, dsum, size_t(B) * sizeof(pal_srp_frame), hipMemcpyDeviceToHost, e->stream), "summary download"));
+  return pal_synchronize(h);
+}
+
+// inputs [strips | pair_weights | seeds] and the output records, one block each; dev(d_strips, d_weights, d_seeds, d_out)
+template <class DEV>
+static int srp_zoom_staged(pal_handle h, Engine* e, const double* strips, int B, int M, int T, const double* pair_weights,
+                           const pal_srp_peak* seeds, int K, pal_srp_zoom_record* out, DEV dev) {
+  if (!strips || !seeds || !out) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  const size_t np = size_t(B) * (size_t(M) * size_t(M - 1) / 2), nk = size_t(B) * size_t(K);
+  Carve ci;
+  const size_t sbytes = np * size_t(2 * T + 1) * sizeof(double);
+  const size_t o_st = ci.take(sbytes), o_w = ci.take(pair_weights ? np * sizeof(double) : 0), o_sd = ci.take(nk * sizeof(pal_srp_peak));
+  char *in = nullptr, *dout = nullptr;
+  PAL_TRY(e->scratch(kWsStageIn, ci.off, &in));
+  PAL_TRY(e->scratch(kWsStageOut, nk * sizeof(pal_srp_zoom_record), &dout));
+  PAL_TRY(e->check(hipMemcpyAsync(in + o_st, strips, sbytes, hipMemcpyHostToDevice, e->stream), "strips upload"));
+  if (pair_weights) PAL_TRY(e->check(hipMemcpyAsync(in + o_w, pair_weights, np * sizeof(double), hipMemcpyHostToDevice, e->stream), "weights upload"));
+  PAL_TRY(e->check(hipMemcpyAsync(in + o_sd, seeds, nk * sizeof(pal_srp_peak), hipMemcpyHostToDevice, e->stream), "seeds upload"));
+  PAL_TRY(dev(reinterpret_cast<const double*>(in + o_st), pair_weights ? reinterpret_cast<const double*>(in + o_w) : nullptr,
+              reinterpret_cast<const pal_srp_peak*>(in + o_sd), reinterpret_cast<pal_srp_zoom_record*>(dout)));
+  PAL_TRY(e->check(hipMemcpyAsync(out, dout, nk * sizeof(pal_srp_zoom_record), hipMemcpyDeviceToHost, e->stream), "zoom download"));
+  return pal_synchronize(h);
+}
+
+}  // extern "C++"
+
+int pal_srp_map_dev(pal_handle h, const double* d_strips, int B, int M, int T, const double* mics, double fs, double c,
+                    const pal_srp_grid* grid, const double* d_pair_weights, int K, int R, double* d_power, pal_srp_peak* d_peaks,
+                    pal_srp_frame* d_summary) {
+  ENGINE(h);
+  return e->srp_map_dev(d_strips, B, M, T, mics, fs, c, grid, d_pair_weights, K, R, d_power, d_peaks, d_summary);
+}
+
+int pal_srp_map(pal_handle h, const double* strips, int B, int M, int T, const double* mics, double fs, double c, const pal_srp_grid* grid,
+                const double* pair_weights, int K, int R, double* power, pal_srp_peak* peaks, pal_srp_frame* summary) {
+  ENGINE(h);
+  PAL_TRY(e->srp_map_check(B, M, T, mics, fs, c, grid, K, R, power || peaks || summary, peaks != nullptr));
+  const size_t G = size_t(grid->count[0]) * size_t(grid->count[1]) * size_t(grid->count[2]);
+  return srp_map_staged(h, e, strips, B, M, T, pair_weights, K, G, power, peaks, summary,
+                        [&](const double* ds, const double* dw, double* dpw, pal_srp_peak* dpk, pal_srp_frame* dsum) {
+                          return e->srp_map_dev(ds, B, M, T, mics, fs, c, grid, dw, K, R, dpw, dpk, dsum);
+                        });
 }
 
 int pal_srp_peaks_dev(pal_handle h, const double* d_power, int B, const pal_srp_grid* grid, int K, int R, pal_srp_peak* d_peaks,
@@ -820,21 +875,10 @@ int pal_srp_peaks(pal_handle h, const double* power, int B, const pal_srp_grid* 
                   pal_srp_frame* summary) {
   ENGINE(h);
   PAL_TRY(e->srp_peaks_check(B, grid, K, R));
-  if (!power || !peaks) return e->fail(PAL_ERR_INVALID, "NULL buffer");
   const size_t G = size_t(grid->count[0]) * size_t(grid->count[1]) * size_t(grid->count[2]);
-  Carve co;
-  const size_t o_pk = co.take(size_t(B) * size_t(K) * sizeof(pal_srp_peak)), o_sum = co.take(summary ? size_t(B) * sizeof(pal_srp_frame) : 0);
-  void* in = nullptr;
-  char* out = nullptr;
-  PAL_TRY(e->scratch(kWsStageIn, size_t(B) * G * sizeof(double), &in));
-  PAL_TRY(e->scratch(kWsStageOut, co.off, &out));
-  PAL_TRY(e->check(hipMemcpyAsync(in, power, size_t(B) * G * sizeof(double), hipMemcpyHostToDevice, e->stream), "map upload"));
-  pal_srp_peak* dpk = reinterpret_cast<pal_srp_peak*>(out + o_pk);
-  pal_srp_frame* dsum = summary ? reinterpret_cast<pal_srp_frame*>(out + o_sum) : nullptr;
-  PAL_TRY(e->srp_peaks_dev(static_cast<const double*>(in), B, grid, K, R, dpk, dsum));
-  PAL_TRY(e->check(hipMemcpyAsync(peaks, dpk, size_t(B) * size_t(K) * sizeof(pal_srp_peak), hipMemcpyDeviceToHost, e->stream), "peaks download"));
-  if (summary) PAL_TRY(e->check(hipMemcpyAsync(summary, dsum, size_t(B) * sizeof(pal_srp_frame), hipMemcpyDeviceToHost, e->stream), "summary download"));
-  return pal_synchronize(h);
+  return srp_peaks_staged(h, e, power, B, K, G, peaks, summary, [&](const double* dp, pal_srp_peak* dpk, pal_srp_frame* dsum) {
+    return e->srp_peaks_dev(dp, B, grid, K, R, dpk, dsum);
+  });
 }
 
 int pal_srp_zoom_dev(pal_handle h, const double* d_strips, int B, int M, int T, const double* mics, double fs, double c,
@@ -849,26 +893,13 @@ int pal_srp_zoom(pal_handle h, const double* strips, int B, int M, int T, const 
                  pal_srp_zoom_record* out) {
   ENGINE(h);
   PAL_TRY(e->srp_zoom_check(B, M, T, mics, fs, c, K, half0, Z, levels));
-  if (!strips || !seeds || !out) return e->fail(PAL_ERR_INVALID, "NULL buffer");
-  const size_t P = size_t(M) * size_t(M - 1) / 2, np = size_t(B) * P, nk = size_t(B) * size_t(K);
-  // staged inputs [strips | pair_weights | seeds] and the output records, one block each
-  Carve ci;
-  const size_t sbytes = np * size_t(2 * T + 1) * sizeof(double);
-  const size_t o_st = ci.take(sbytes), o_w = ci.take(pair_weights ? np * sizeof(double) : 0), o_sd = ci.take(nk * sizeof(pal_srp_peak));
-  char *in = nullptr, *dout = nullptr;
-  PAL_TRY(e->scratch(kWsStageIn, ci.off, &in));
-  PAL_TRY(e->scratch(kWsStageOut, nk * sizeof(pal_srp_zoom_record), &dout));
-  PAL_TRY(e->check(hipMemcpyAsync(in + o_st, strips, sbytes, hipMemcpyHostToDevice, e->stream), "strips upload"));
-  if (pair_weights) PAL_TRY(e->check(hipMemcpyAsync(in + o_w, pair_weights, np * sizeof(double), hipMemcpyHostToDevice, e->stream), "weights upload"));
-  PAL_TRY(e->check(hipMemcpyAsync(in + o_sd, seeds, nk * sizeof(pal_srp_peak), hipMemcpyHostToDevice, e->stream), "seeds upload"));
-  PAL_TRY(e->srp_zoom_dev(reinterpret_cast<const double*>(in + o_st), B, M, T, mics, fs, c,
-                          pair_weights ? reinterpret_cast<const double*>(in + o_w) : nullptr, reinterpret_cast<const pal_srp_peak*>(in + o_sd), K,
-                          half0, Z, levels, reinterpret_cast<pal_srp_zoom_record*>(dout)));
-  PAL_TRY(e->check(hipMemcpyAsync(out, dout, nk * sizeof(pal_srp_zoom_record), hipMemcpyDeviceToHost, e->stream), "zoom download"));
-  return pal_synchronize(h);
+  return srp_zoom_staged(h, e, strips, B, M, T, pair_weights, seeds, K, out,
+                         [&](const double* ds, const double* dw, const pal_srp_peak* dsd, pal_srp_zoom_record* dout) {
+                           return e->srp_zoom_dev(ds, B, M, T, mics, fs, c, dw, dsd, K, half0, Z, levels, dout);
+                         });
 }
 
-// ---- the direction map (srp_doa.hip): staged through the blocks of pal_srp_map, pal_srp_peaks and pal_srp_zoom ----
+// ---- the direction map (srp.hip): the same staged forms with G = n_az * n_el ----
 int pal_srp_doa_dev(pal_handle h, const double* d_strips, int B, int M, int T, const double* mics, double fs, double c,
                     const pal_srp_doa_grid* grid, const double* az, const double* el, const double* d_pair_weights, int K, int R,
                     double* d_power, pal_srp_peak* d_peaks, pal_srp_frame* d_summary) {
@@ -881,29 +912,10 @@ int pal_srp_doa(pal_handle h, const double* strips, int B, int M, int T, const d
                 pal_srp_peak* peaks, pal_srp_frame* summary) {
   ENGINE(h);
   PAL_TRY(e->srp_doa_check(B, M, T, mics, fs, c, grid, az, el, K, R, power || peaks || summary, peaks != nullptr));
-  if (!strips) return e->fail(PAL_ERR_INVALID, "NULL buffer");
-  const size_t P = size_t(M) * size_t(M - 1) / 2, np = size_t(B) * P;
-  const size_t G = size_t(grid->n_az) * size_t(grid->n_el);
-  // staged inputs [strips | pair_weights] and outputs [power | peaks | summary], one block each
-  Carve ci, co;
-  const size_t sbytes = np * size_t(2 * T + 1) * sizeof(double);
-  const size_t o_st = ci.take(sbytes), o_w = ci.take(pair_weights ? np * sizeof(double) : 0);
-  const size_t o_pw = co.take(power ? size_t(B) * G * sizeof(double) : 0), o_pk = co.take(peaks ? size_t(B) * size_t(K) * sizeof(pal_srp_peak) : 0);
-  const size_t o_sum = co.take(summary ? size_t(B) * sizeof(pal_srp_frame) : 0);
-  char *in = nullptr, *out = nullptr;
-  PAL_TRY(e->scratch(kWsStageIn, ci.off, &in));
-  PAL_TRY(e->scratch(kWsStageOut, co.off, &out));
-  PAL_TRY(e->check(hipMemcpyAsync(in + o_st, strips, sbytes, hipMemcpyHostToDevice, e->stream), "strips upload"));
-  if (pair_weights) PAL_TRY(e->check(hipMemcpyAsync(in + o_w, pair_weights, np * sizeof(double), hipMemcpyHostToDevice, e->stream), "weights upload"));
-  double* dpw = power ? reinterpret_cast<double*>(out + o_pw) : nullptr;
-  pal_srp_peak* dpk = peaks ? reinterpret_cast<pal_srp_peak*>(out + o_pk) : nullptr;
-  pal_srp_frame* dsum = summary ? reinterpret_cast<pal_srp_frame*>(out + o_sum) : nullptr;
-  PAL_TRY(e->srp_doa_dev(reinterpret_cast<const double*>(in + o_st), B, M, T, mics, fs, c, grid, az, el,
-                         pair_weights ? reinterpret_cast<const double*>(in + o_w) : nullptr, K, R, dpw, dpk, dsum));
-  if (power) PAL_TRY(e->check(hipMemcpyAsync(power, dpw, size_t(B) * G * sizeof(double), hipMemcpyDeviceToHost, e->stream), "map download"));
-  if (peaks) PAL_TRY(e->check(hipMemcpyAsync(peaks, dpk, size_t(B) * size_t(K) * sizeof(pal_srp_peak), hipMemcpyDeviceToHost, e->stream), "peaks download"));
-  if (summary) PAL_TRY(e->check(hipMemcpyAsync(summary, dsum, size_t(B) * sizeof(pal_srp_frame), hipMemcpyDeviceToHost, e->stream), "summary download"));
-  return pal_synchronize(h);
+  return srp_map_staged(h, e, strips, B, M, T, pair_weights, K, size_t(grid->n_az) * size_t(grid->n_el), power, peaks, summary,
+                        [&](const double* ds, const double* dw, double* dpw, pal_srp_peak* dpk, pal_srp_frame* dsum) {
+                          return e->srp_doa_dev(ds, B, M, T, mics, fs, c, grid, az, el, dw, K, R, dpw, dpk, dsum);
+                        });
 }
 
 int pal_srp_doa_peaks_dev(pal_handle h, const double* d_power, int B, const pal_srp_doa_grid* grid, const double* az, const double* el,
@@ -916,21 +928,10 @@ int pal_srp_doa_peaks(pal_handle h, const double* power, int B, const pal_srp_do
                       int R, pal_srp_peak* peaks, pal_srp_frame* summary) {
   ENGINE(h);
   PAL_TRY(e->srp_doa_peaks_check(B, grid, az, el, K, R));
-  if (!power || !peaks) return e->fail(PAL_ERR_INVALID, "NULL buffer");
-  const size_t G = size_t(grid->n_az) * size_t(grid->n_el);
-  Carve co;
-  const size_t o_pk = co.take(size_t(B) * size_t(K) * sizeof(pal_srp_peak)), o_sum = co.take(summary ? size_t(B) * sizeof(pal_srp_frame) : 0);
-  void* in = nullptr;
-  char* out = nullptr;
-  PAL_TRY(e->scratch(kWsStageIn, size_t(B) * G * sizeof(double), &in));
-  PAL_TRY(e->scratch(kWsStageOut, co.off, &out));
-  PAL_TRY(e->check(hipMemcpyAsync(in, power, size_t(B) * G * sizeof(double), hipMemcpyHostToDevice, e->stream), "map upload"));
-  pal_srp_peak* dpk = reinterpret_cast<pal_srp_peak*>(out + o_pk);
-  pal_srp_frame* dsum = summary ? reinterpret_cast<pal_srp_frame*>(out + o_sum) : nullptr;
-  PAL_TRY(e->srp_doa_peaks_dev(static_cast<const double*>(in), B, grid, az, el, K, R, dpk, dsum));
-  PAL_TRY(e->check(hipMemcpyAsync(peaks, dpk, size_t(B) * size_t(K) * sizeof(pal_srp_peak), hipMemcpyDeviceToHost, e->stream), "peaks download"));
-  if (summary) PAL_TRY(e->check(hipMemcpyAsync(summary, dsum, size_t(B) * sizeof(pal_srp_frame), hipMemcpyDeviceToHost, e->stream), "summary download"));
-  return pal_synchronize(h);
+  return srp_peaks_staged(h, e, power, B, K, size_t(grid->n_az) * size_t(grid->n_el), peaks, summary,
+                          [&](const double* dp, pal_srp_peak* dpk, pal_srp_frame* dsum) {
+                            return e->srp_doa_peaks_dev(dp, B, grid, az, el, K, R, dpk, dsum);
+                          });
 }
 
 int pal_srp_doa_zoom_dev(pal_handle h, const double* d_strips, int B, int M, int T, const double* mics, double fs, double c,
@@ -945,23 +946,10 @@ int pal_srp_doa_zoom(pal_handle h, const double* strips, int B, int M, int T, co
                      pal_srp_zoom_record* out) {
   ENGINE(h);
   PAL_TRY(e->srp_doa_zoom_check(B, M, T, mics, fs, c, K, half0, Z, levels));
-  if (!strips || !seeds || !out) return e->fail(PAL_ERR_INVALID, "NULL buffer");
-  const size_t P = size_t(M) * size_t(M - 1) / 2, np = size_t(B) * P, nk = size_t(B) * size_t(K);
-  // staged inputs [strips | pair_weights | seeds] and the output records, one block each
-  Carve ci;
-  const size_t sbytes = np * size_t(2 * T + 1) * sizeof(double);
-  const size_t o_st = ci.take(sbytes), o_w = ci.take(pair_weights ? np * sizeof(double) : 0), o_sd = ci.take(nk * sizeof(pal_srp_peak));
-  char *in = nullptr, *dout = nullptr;
-  PAL_TRY(e->scratch(kWsStageIn, ci.off, &in));
-  PAL_TRY(e->scratch(kWsStageOut, nk * sizeof(pal_srp_zoom_record), &dout));
-  PAL_TRY(e->check(hipMemcpyAsync(in + o_st, strips, sbytes, hipMemcpyHostToDevice, e->stream), "strips upload"));
-  if (pair_weights) PAL_TRY(e->check(hipMemcpyAsync(in + o_w, pair_weights, np * sizeof(double), hipMemcpyHostToDevice, e->stream), "weights upload"));
-  PAL_TRY(e->check(hipMemcpyAsync(in + o_sd, seeds, nk * sizeof(pal_srp_peak), hipMemcpyHostToDevice, e->stream), "seeds upload"));
-  PAL_TRY(e->srp_doa_zoom_dev(reinterpret_cast<const double*>(in + o_st), B, M, T, mics, fs, c,
-                              pair_weights ? reinterpret_cast<const double*>(in + o_w) : nullptr,
-                              reinterpret_cast<const pal_srp_peak*>(in + o_sd), K, half0, Z, levels, reinterpret_cast<pal_srp_zoom_record*>(dout)));
-  PAL_TRY(e->check(hipMemcpyAsync(out, dout, nk * sizeof(pal_srp_zoom_record), hipMemcpyDeviceToHost, e->stream), "zoom download"));
-  return pal_synchronize(h);
+  return srp_zoom_staged(h, e, strips, B, M, T, pair_weights, seeds, K, out,
+                         [&](const double* ds, const double* dw, const pal_srp_peak* dsd, pal_srp_zoom_record* dout) {
+                           return e->srp_doa_zoom_dev(ds, B, M, T, mics, fs, c, dw, dsd, K, half0, Z, levels, dout);
+                         });
 }
 
 static int single_pair(Engine* e, const double* sig1, int n1, const double* sig2, int n2, const pal_phat_params* prm,

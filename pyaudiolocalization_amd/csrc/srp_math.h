@@ -1,4 +1,4 @@
-// srp_math.h - the arithmetic of the steered-response power map (srp.hip; specification: pyaudiolocalization_amd/srp.py) for host and
+// srp_math.h - the arithmetic of the steered-response power maps (srp.hip, srp_cells.h; specification: pyaudiolocalization_amd/srp.py) for host and
 // device: the grid point, the distance, the lag with its clip test, the smoothing sum of a lag strip and the neighbourhood rule of the
 // map's peaks.  Every function gives the specification's bits, so it is compiled with -ffp-contract=off wherever it is used: a product
 // is rounded before it is added.  No HIP runtime calls; tests/host/test_srp_math.cpp, tests/host/test_srp_zoom.cpp (the zoom's
@@ -121,13 +121,18 @@ PAL_SRP_HD bool srp_zoom_clipped(double k, int T) { return !(k >= double(-T) && 
 // s0 + f * (s1 - s0), f = q - k in [0, 1]: the product is rounded before the addition
 PAL_SRP_HD double srp_blend(double s0, double s1, double f) { return s0 + f * (s1 - s0); }
 
-// one term of a point's power from row[-T .. T], the centre of pair p's strip (row = strips[p] + T); false: clipped, *v untouched
+// the term at a quotient that is not clipped, from row[-T .. T], the centre of pair p's strip (row = strips[p] + T)
+PAL_SRP_HD double srp_zoom_read(const double* row, double q) {
+  const double k = srp_zoom_floor(q);
+  const int at = int(k);
+  return srp_blend(row[at], row[at + 1], q - k);
+}
+
+// one term of a point's power; false: clipped, *v untouched.  The kernels take the same three steps through SrpBlendTerm (srp_cells.h)
 PAL_SRP_HD bool srp_zoom_term(const double* row, int T, double di, double dj, double fs, double c, double* v) {
   const double q = srp_zoom_quotient(di, dj, fs, c);
-  const double k = srp_zoom_floor(q);
-  if (srp_zoom_clipped(k, T)) return false;
-  const int at = int(k);
-  *v = srp_blend(row[at], row[at + 1], q - k);
+  if (srp_zoom_clipped(srp_zoom_floor(q), T)) return false;
+  *v = srp_zoom_read(row, q);
   return true;
 }
 
@@ -159,7 +164,8 @@ PAL_SRP_HD void srp_doa_direction(double ca, double sa, double ce, double se, do
 }
 
 // how far the plane wave from direction u reaches microphone m before it reaches the origin: d_j - d_i = a_i - a_j, so the lag of pair
-// (i, j) is srp_lag(a_j, a_i, ...) and the zoom's term srp_zoom_term(row, T, a_j, a_i, ...)
+// (i, j) is srp_lag(a_j, a_i, ...) and the zoom's term srp_zoom_term(row, T, a_j, a_i, ...).  The kernels pass (-a_i, -a_j) in the
+// near field's order instead (srp_cells.h): negation is exact, so (-a_j) - (-a_i) has the bits of a_i - a_j
 PAL_SRP_HD double srp_doa_advance(double ux, double uy, double uz, double mx, double my, double mz) {
   double a = ux * mx;
   a = a + uy * my;

@@ -1,14 +1,23 @@
-// srp_select.h - what k_srp_peaks (srp.hip) and k_srp_doa_peaks (srp_doa.hip) share: the K selection passes over one frame's marked
-// map.  The two kernels differ in how a cell is marked (the box neighbourhood, or the direction grid's with azimuth wrapped) and in
-// what a record's x, y, z hold (`pos`); the order of the peaks, the absent entries and the summary are one rule.
+// srp_select.h - the body of k_srp_peaks and k_srp_doa_peaks (srp.hip): one frame's marks, then the K selection passes over the marked
+// map.  The two kernels differ in how a cell is marked (`mark`: the box neighbourhood, or the direction grid's with azimuth wrapped)
+// and in what a record's x, y, z hold (`pos`); the order of the peaks, the absent entries and the summary are one rule.
 #pragma once
 #include "engine.h"
 #include "srp_math.h"
 
 namespace pal {
 
-constexpr int kSrpThreads = 256;
 constexpr int kSrpPeakThreads = 1024;
+
+// what both peak kernels are told (srp.hip: launch_peaks fills it)
+struct SrpPeakIo {
+  const double* power;                  // [B][G]
+  unsigned char* marks;                 // [B][G] (K > 0)
+  pal_srp_peak* peaks;                  // [B][K] or nullptr
+  pal_srp_frame* summary;               // [B] or nullptr
+  const unsigned long long* clipped;    // [B] or nullptr (then 0)
+  int G, K;
+};
 
 // One workgroup of kSrpPeakThreads, after the barrier behind its marks: pass k takes the block maximum - in the order power
 // descending, index ascending - of the marked cells behind pass k - 1's pick, and thread 0 writes peaks[k] (absent: index -1, all else
@@ -68,6 +77,22 @@ __device__ __forceinline__ void srp_select_peaks(const double* power, const unsi
     s.reserved = 0;
     *summary = s;
   }
+}
+
+// A peak kernel's whole body, one workgroup per frame: mark(power, g) says whether cell g of this frame's map is a peak.
+template <class MARK, class POS>
+__device__ __forceinline__ void srp_peaks_frame(const SrpPeakIo& a, MARK mark, POS pos) {
+  __shared__ double best_p[kSrpPeakThreads];
+  __shared__ int best_g[kSrpPeakThreads];
+  const int tid = threadIdx.x, b = blockIdx.x, G = a.G;
+  const double* power = a.power + size_t(b) * size_t(G);
+  unsigned char* marks = a.marks + size_t(b) * size_t(G);
+  if (a.K > 0) {
+    for (int g = tid; g < G; g += kSrpPeakThreads) marks[g] = mark(power, g) ? 1 : 0;
+  }
+  __syncthreads();
+  srp_select_peaks(power, marks, G, a.K, a.peaks ? a.peaks + size_t(b) * size_t(a.K) : nullptr, a.summary ? a.summary + b : nullptr,
+                   a.clipped ? a.clipped + b : nullptr, best_p, best_g, pos);
 }
 
 }  // namespace pal

@@ -21,7 +21,7 @@ index mapping plays no part, and several sources show as several maxima.  Conven
 - the map is piecewise constant in space (``rint`` picks one sample), so below about c / fs a finer grid finds plateaus.  The **zoom**
   (``zoom``) refines a peak with a continuous rule instead: the strip read at the fractional lag with linear interpolation, over small
   boxes that shrink around the best cell, the terms added in the fixed order ``tile_order``;
-- the **direction map** (``doa_map``, ``doa_peaks``, ``doa_zoom``; pal_srp_doa*, csrc/srp_doa.hip) sums the same strips over a grid of
+- the **direction map** (``doa_map``, ``doa_peaks``, ``doa_zoom``; pal_srp_doa*, csrc/srp.hip) sums the same strips over a grid of
   azimuth and elevation under the plane-wave model, for arrays that resolve direction and not range: see the section at the end.
 
 Every product is rounded before it is added (no fused multiply-add), square root and division are correctly rounded and rint rounds

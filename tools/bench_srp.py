@@ -138,7 +138,7 @@ zoom_out = {
                              "zoomed_to_source_m": d_cz},
 }
 
-# the direction map (csrc/srp_doa.hip) on the same strips: two spheres and the zoom on each one's peaks, against the `grid`^3 map
+# the direction map (csrc/srp.hip) on the same strips: two spheres and the zoom on each one's peaks, against the `grid`^3 map
 src_dir = sources / np.linalg.norm(sources, axis=1, keepdims=True)                   # the array's centre is the origin
 
 

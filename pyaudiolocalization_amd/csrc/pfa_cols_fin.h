@@ -457,6 +457,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
   static_assert(!R89 || (NW == 4 && FULL), "the Rader column transform is the four-wavefront N1 = 89 case");
   static_assert(!HIST || NW <= 4, "the histogram form merges at most four wavefronts per block");
   static_assert(!(HIST && STRIP), "the strip form belongs to the per-wavefront statistics");
+  static_assert(!STRIP || NW >= 2, "the strip form's rows are finished by wavefronts 0 and 1, one row each");
   const cd* __restrict__ Y = src.Y;
   const double* __restrict__ T = src.T;
   const Rader89Tab* __restrict__ tab = src.tab;
@@ -550,6 +551,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(MODE ==
                                                    active && (c_lo == 0 || c_hi == N2), -1, true, pa, fa);
     }
     if (!last) return;
+    if constexpr (STRIP) {                                     // strip form: wavefronts 0 and 1 finish one row each (NW >= 2)
+      if (wave >= 2 || 2 * g + wave >= rows) return;
+      fin_rows_wave<true>(pa, fa, g, nblk, rows, N1, N2, lane, wave, wave + 1);
+      return;
+    }
     if (wave != 0) return;                                     // ONE wavefront finishes the transform's rows (fin_row_wave)
     fin_rows_wave<STRIP>(pa, fa, g, nblk, rows, N1, N2, lane);
     return;

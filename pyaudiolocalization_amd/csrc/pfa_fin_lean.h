@@ -23,6 +23,8 @@
 //     call said it would not (fin_window_direct).  Polling form (no lag window, a strip above kFinStripShare of the row,
 //     PAL_FIN_STRIP=0): the wavefront polls the siblings' maxima and sums its own samples inside the window - a wait of about
 //     3000 of its 13 350 wave cycles on the metric run (profiles/r03_c_fin_ablation.txt), which is what the strip form removes.
+//     In the strip form TWO wavefronts of the transform's last block finish one row each (fin_rows_wave): a row's finish is a chain
+//     of device-scope round trips during which that block holds its slot, and the two rows' chains are independent.
 //
 // Semantics are those of pfa_cols_fin.h's general path with per-wavefront instead of per-block search floors (a floor only
 // prunes the candidate search; a wavefront whose bounded search finds no strict peak searches all its samples).
@@ -508,9 +510,12 @@ __device__ __forceinline__ void fin_row_wave(const PeakArgs& pa, const FinArgs& 
 }
 
 // ---- the tail of a per-wavefront pass, in wavefront 0 of the transform's last block: wait for every wavefront's `done` word, then
-//      finish rows 2 g and 2 g + 1.  When the siblings' results are not there in time both rows go through the stored-row path instead
+//      finish rows 2 g and 2 g + 1.  When the siblings' results are not there in time both rows go through the stored-row path instead.
+//      Strip form: wavefronts 0 and 1 of that block, ONE row each (r_lo = wave, r_hi = wave + 1) - a row's finish is a chain of round
+//      trips to the scratch, the two rows' chains are independent, and the block's slot is held until the last of them ends
 template <bool STRIP = false>
-__device__ __forceinline__ void fin_rows_wave(const PeakArgs& pa, const FinArgs& fa, int g, int nblk, int rows, int N1, int N2, int lane) {
+__device__ __forceinline__ void fin_rows_wave(const PeakArgs& pa, const FinArgs& fa, int g, int nblk, int rows, int N1, int N2, int lane,
+                                              int r_lo = 0, int r_hi = 2) {
   bool late = fa.giveup != 0;                                  // (PAL_DEBUG_FIN_GIVEUP=1: no polls, both rows flagged)
   for (int q = lane; !fa.giveup && q < nblk * fa.pw; q += 64) {
     int spins = 0;
@@ -520,11 +525,11 @@ __device__ __forceinline__ void fin_rows_wave(const PeakArgs& pa, const FinArgs&
     }
   }
   if (__ballot(late)) {
-    if (lane < 2 && 2 * g + lane < rows) { fa.need[2 * g + lane] = 1; atomicAdd(fa.status + kStFlagged, 1); atomicAdd(fa.status + kStGaveUp, 1); }
+    if (lane >= r_lo && lane < r_hi && 2 * g + lane < rows) { fa.need[2 * g + lane] = 1; atomicAdd(fa.status + kStFlagged, 1); atomicAdd(fa.status + kStGaveUp, 1); }
     return;
   }
 #pragma nounroll
-  for (int r = 0; r < 2; ++r)
+  for (int r = r_lo; r < r_hi; ++r)
     if (2 * g + r < rows) fin_row_wave<STRIP>(pa, fa, 2 * g + r, N1, N2, lane);
 }
 

@@ -483,6 +483,17 @@ int pal_steer_sum(pal_handle h, const double* frames, int B, int M, int L, doubl
                   double* out);
 int pal_steer_sum_dev(pal_handle h, const double* d_frames, int B, int M, int L, double fs, const double* d_delays,
                       const double* d_weights, int S, double* d_out);
+/* Null-steering beamformer (specification: pyaudiolocalization_amd/beamform.py, separate): the S beams of a frame cancel each other's
+ * sources.  Per frequency bin Z = (G + delta I)^-1 Y, with Y the delay-and-sum spectra of pal_steer_sum at weights = gains, G the S x S
+ * Gram matrix of the steering vectors gains[b][s][m] exp(j 2 pi f delays[b][s][m]) and delta = loading * max_s sum_m gains[b][s][m]^2;
+ * out[b][s] = ifft(Z[s]).real[:L] * fade_window(L).  With S = 1 and loading 0 that is pal_steer_sum at weights gains / sum_m gains^2.
+ * Everything pal_steer_sum refuses is refused the same way; also PAL_ERR_INVALID: loading negative or not finite, loading == 0 with
+ * S > 1 (bin 0 of G is singular); PAL_ERR_UNSUPPORTED: S > 8.  A source whose gains are all zero is a row of exact zeros beside the
+ * others, a frame without a live weighted row is S rows of exact zeros.  The _dev form is asynchronous like pal_steer_sum_dev. */
+int pal_separate(pal_handle h, const double* frames, int B, int M, int L, double fs, const double* delays, const double* gains, int S,
+                 double loading, double* out);
+int pal_separate_dev(pal_handle h, const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_gains,
+                     int S, double loading, double* d_out);
 /* normalize_signal (normalize_only != 0) or dynamic_range_compression (signal_processing.py:82-94) */
 int pal_normalize_compress(pal_handle h, const double* rows, int R, int N, int normalize_only, double threshold,
                            double epsilon, double* out);

@@ -160,6 +160,10 @@ SIGNATURES = {
     "pal_fractional_delay": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p]),
     "pal_steer_sum": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pal_steer_sum_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pal_separate": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                               C.c_void_p]),
+    "pal_separate_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                   C.c_void_p]),
     "pal_normalize_compress": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "pal_filtfilt": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                C.c_void_p]),

@@ -1,6 +1,6 @@
-"""Delay-and-sum beamformer: the specification of ``Engine.steer`` (csrc/beamform.hip) and the helpers that turn positions,
-directions and SRP records into steering delays.  Pure NumPy, no engine call - the role closure.py, consensus.py and srp.py play for
-their features.
+"""Delay-and-sum and null-steering beamformers: the specifications of ``Engine.steer`` and ``Engine.separate`` (csrc/beamform.hip) and
+the helpers that turn positions, directions and SRP records into steering delays.  Pure NumPy, no engine call - the role closure.py,
+consensus.py and srp.py play for their features.
 
 ``steer(frames[B][M][L], fs, delays[B][S][M], weights[B][S][M]) -> out[B][S][L]``::
 
@@ -15,6 +15,25 @@ delayed so that the chosen point lines up, then the rows are summed.  With ``M``
 ``10 log10(M)`` dB over one microphone.
 
 Delays are >= 0 in what the helpers return (the farthest, or latest, microphone gets 0); ``steer`` itself takes any sign.
+
+``separate(frames[B][M][L], fs, delays[B][S][M], gains[B][S][M], loading) -> out[B][S][L]`` is the beamformer that cancels the other
+sources: with the S positions known, the S beams of a bin are the least-squares solution of ``X = A s``, ``A[m,s] = gains[b,s,m] *
+conj(p[s,m])`` the steering matrix (null steering / zero forcing with diagonal loading, an LCMV beamformer under white noise)::
+
+    p[s,m]   = np.exp(-1j*2*np.pi*f*delays[b,s,m])
+    Y[s]     = 0;  for m = 0 .. M-1:  Y[s] = Y[s] + gains[b,s,m] * (X[b,m] * p[s,m])                      (steer's sum, weights = gains)
+    G[s,t]   = 0;  for m = 0 .. M-1:  G[s,t] = G[s,t] + (gains[b,s,m]*gains[b,t,m]) * (p[s,m] * np.conj(p[t,m]))     for t < s
+    q[s]     = 0;  for m = 0 .. M-1:  q[s] = q[s] + gains[b,s,m]*gains[b,s,m]                             (G's diagonal, every bin's)
+    delta    = loading * max_s q[s]
+    Z        = solve_loaded(q + delta, G, Y)            ((G + delta I) Z = Y by Cholesky; its docstring states the operation order)
+    out[b,s] = np.fft.ifft(Z[s]).real[:L] * fade_window(L)
+
+Consequences: ``Z(-f) = conj(Z(f))``, so L + 1 bins carry everything (the device computes those, and only the real part of the Nyquist
+bin survives ``.real``).  With S = 1 and loading 0 the result is ``steer(frames, fs, delays, gains / q)``.  A source whose gains are
+all zero has a zero row and column in G: its output is a row of exact zeros and the others do not notice it.  A frame without a live
+weighted row gives S rows of exact zeros.  Two sources with the same delays do not break the solve (delta > 0 keeps the factor
+positive) and give two equal rows.  ``cond(G + delta I) <= (S + loading) / loading`` where q is equal across sources, and
+``|(G + delta I)^-1| <= 1 / delta`` always - the bound the test tolerances rest on.
 """
 from __future__ import annotations
 
@@ -57,6 +76,100 @@ def steer(frames, fs, delays, weights) -> np.ndarray:
         product = spec[:, None, m, :] * phase
         acc = acc + w[:, :, m, None] * product
     return np.fft.ifft(acc, axis=-1).real[..., :length] * fade_window(length)
+
+
+def solve_loaded(diag, g, y):
+    """(G + delta I) z = y for Hermitian positive definite systems of n unknowns, vectorised over any trailing axes (the bins):
+    ``diag[n][...]`` is the real diagonal G[i][i] + delta, ``g[n][n][...]`` complex of which only the strict lower triangle is read,
+    ``y[n][...]`` complex.  -> z[n][...].  Cholesky, on real and imaginary parts with every product written out, so that the bits do
+    not depend on how a library multiplies complex numbers (csrc/separate_math.h runs the same operations in the same order)::
+
+        factor, j = 0 .. n-1:   s = diag[j];  for k = 0 .. j-1:  s = s - (Lre[j,k]*Lre[j,k] + Lim[j,k]*Lim[j,k])
+                                r[j] = 1 / sqrt(s)
+                                for i = j+1 .. n-1:  v = g[i,j];  for k = 0 .. j-1:  v = v - L[i,k] conj(L[j,k]);   L[i,j] = v * r[j]
+        forward, i = 0 .. n-1:  v = y[i];  for k = 0 .. i-1:    v = v - L[i,k] z[k];         z[i] = v * r[i]
+        back, i = n-1 .. 0:     v = z[i];  for k = i+1 .. n-1:  v = v - conj(L[k,i]) z[k];   z[i] = v * r[i]
+
+    (a+jb)(c+jd) = (a*c - b*d) + j(a*d + b*c), (a+jb) conj(c+jd) = (a*c + b*d) + j(b*c - a*d), conj(a+jb)(c+jd) = (a*c + b*d) +
+    j(a*d - b*c): each bracket is formed first, then subtracted from the running part."""
+    g = np.asarray(g, dtype=np.complex128)
+    y = np.asarray(y, dtype=np.complex128)
+    n = y.shape[0]
+    tail = np.broadcast_shapes(g.shape[2:], y.shape[1:], np.shape(diag)[1:])
+    dg = np.broadcast_to(np.asarray(diag, dtype=np.float64), (n,) + tail)
+    lre = np.array(np.broadcast_to(g.real, (n, n) + tail))
+    lim = np.array(np.broadcast_to(g.imag, (n, n) + tail))
+    zre = np.array(np.broadcast_to(y.real, (n,) + tail))
+    zim = np.array(np.broadcast_to(y.imag, (n,) + tail))
+    r = np.empty((n,) + tail)
+    for j in range(n):
+        s = dg[j].copy()
+        for k in range(j):
+            s = s - (lre[j, k] * lre[j, k] + lim[j, k] * lim[j, k])
+        r[j] = 1.0 / np.sqrt(s)
+        for i in range(j + 1, n):
+            vre, vim = lre[i, j], lim[i, j]
+            for k in range(j):
+                a, b, c, d = lre[i, k], lim[i, k], lre[j, k], lim[j, k]
+                vre = vre - (a * c + b * d)
+                vim = vim - (b * c - a * d)
+            lre[i, j] = vre * r[j]
+            lim[i, j] = vim * r[j]
+    for i in range(n):
+        vre, vim = zre[i], zim[i]
+        for k in range(i):
+            a, b, c, d = lre[i, k], lim[i, k], zre[k], zim[k]
+            vre = vre - (a * c - b * d)
+            vim = vim - (a * d + b * c)
+        zre[i] = vre * r[i]
+        zim[i] = vim * r[i]
+    for i in range(n - 1, -1, -1):
+        vre, vim = zre[i], zim[i]
+        for k in range(i + 1, n):
+            a, b, c, d = lre[k, i], lim[k, i], zre[k], zim[k]
+            vre = vre - (a * c + b * d)
+            vim = vim - (a * d - b * c)
+        zre[i] = vre * r[i]
+        zim[i] = vim * r[i]
+    return zre + 1j * zim
+
+
+def check_loading(loading, s: int) -> float:
+    """loading >= 0 and finite; 0 only with one source (bin 0 of G is the singular all-ones matrix otherwise)"""
+    loading = float(loading)
+    if not np.isfinite(loading) or loading < 0:
+        raise ValueError("loading must be finite and >= 0")
+    if loading == 0 and s > 1:
+        raise ValueError("loading 0 is for one source only: bin 0 of the steering matrix's Gram matrix is singular")
+    return loading
+
+
+def separate(frames, fs, delays, gains, loading=0.01) -> np.ndarray:
+    """frames[B][M][L], delays / gains[B][S][M] -> out[B][S][L]: the null-steering beams (the rule in the module's docstring, m
+    ascending, the solve in solve_loaded's order).  A source without gains has the diagonal delta, or 1 where delta is 0 too: its
+    row and column of G are zeros, so the value only keeps the factor finite."""
+    x, d, g = _tables(frames, delays, gains)
+    b, s, _ = d.shape
+    loading = check_loading(loading, s)
+    length = x.shape[2]
+    spec = np.fft.fft(x, n=2 * length, axis=-1)                                 # [B][M][2L]
+    f = np.fft.fftfreq(2 * length, d=1.0 / fs)
+    y = np.zeros((b, s, 2 * length), dtype=np.complex128)
+    gram = np.zeros((b, s, s, 2 * length), dtype=np.complex128)
+    q = np.zeros((b, s))
+    for m in range(x.shape[1]):
+        phase = np.exp(-1j * 2 * np.pi * f[None, None, :] * d[:, :, m, None])
+        product = spec[:, None, m, :] * phase
+        y = y + g[:, :, m, None] * product
+        q = q + g[:, :, m] * g[:, :, m]
+        for i in range(s):
+            for t in range(i):
+                gram[:, i, t] = gram[:, i, t] + (g[:, i, m] * g[:, t, m])[:, None] * (phase[:, i] * np.conj(phase[:, t]))
+    delta = loading * np.max(q, axis=1)                                         # [B]
+    diag = q + delta[:, None]
+    diag = np.where(diag == 0.0, 1.0, diag)
+    z = solve_loaded(np.moveaxis(diag, 0, 1)[:, :, None], np.moveaxis(gram, 0, 2), np.moveaxis(y, 0, 1))   # [S][B][2L]
+    return np.fft.ifft(np.moveaxis(z, 0, 1), axis=-1).real[..., :length] * fade_window(length)
 
 
 def _calibrated(d: np.ndarray, calib_delays) -> np.ndarray:

@@ -7,10 +7,13 @@
 // S beam spectra of every frame while it reads each microphone spectrum once per tile of up to 8 beams, and the beams go through the
 // exact-length inverse DFT(2L) two rows per complex transform (BeamLoader -> launch_cols_fwd / launch_rows / launch_cols_inv ->
 // SimStorer: fade window, exponent put back).  Built with -ffp-contract=off: the operation order below is what runs.
+// The null-steering beamformer (beamform.py, separate) is the same path with k_separate_frame and k_separate in k_steer_sum's place:
+// the S beam spectra of a bin are solved against the Gram matrix of the S steering vectors, so each beam cancels the other sources.
 #include <cmath>
 
 #include "conv_kernels.h"
 #include "reduce.h"
+#include "separate_math.h"
 #include "sim_rows.h"
 
 namespace pal {
@@ -105,6 +108,138 @@ __global__ __launch_bounds__(256) void k_steer_sum(const cd* __restrict__ X, con
   }
 }
 
+// What the null-steering beams of one frame share and no bin changes: q[s] = sum_m g[s,m]^2 (the real diagonal of G), top[s] = sum_m
+// |g[s,m]| 2^e_m over the live rows as in k_steer_sum, both m ascending; delta = loading max_s q[s]; the loaded diagonal q[s] + delta (1
+// where that is 0: a source without gains under loading 0, whose row and column of G are zeros).
+// Exponents: the rows of a frame are coupled by the solve, so one exponent serves them all, e = ilogb((sum_t top_t) / delta), t
+// ascending (|(G + delta I)^-1| <= 1 / delta; with loading 0, one source, the divisor is q[0]); it goes into each of the frame's S
+// entries of beam_exp.  A frame without a live weighted row is S dead beams; a source without gains is a dead beam beside live ones.
+// One workgroup of one wavefront per frame, lane s sums source s.
+__global__ __launch_bounds__(64) void k_separate_frame(const int* __restrict__ flags, const double* __restrict__ gains, int M, int S,
+                                                       double loading, double* __restrict__ diag, int* __restrict__ beam_exp,
+                                                       int* __restrict__ beam_live) {
+  __shared__ double stop[kSeparateMax], sq[kSeparateMax];
+  const int f = blockIdx.x, q = threadIdx.x;
+  if (q < S) {
+    const double* g = gains + (size_t(f) * size_t(S) + size_t(q)) * size_t(M);
+    const int* fl = flags + size_t(f) * size_t(M);
+    double top = 0.0, qq = 0.0;
+    for (int m = 0; m < M; ++m) {
+      const double w = g[m];
+      const double amp = fl[m] ? ldexp(1.0, flag_exponent(fl[m])) : 0.0;   // 2^e_m of a live row
+      top = top + fabs(w) * amp;
+      qq = qq + w * w;
+    }
+    stop[q] = top;
+    sq[q] = qq;
+  }
+  __syncthreads();
+  if (q < S) {
+    double sumtop = 0.0, qmax = 0.0;
+    for (int t = 0; t < S; ++t) {
+      sumtop = sumtop + stop[t];
+      qmax = sq[t] > qmax ? sq[t] : qmax;
+    }
+    const bool alive = sumtop > 0.0;
+    const double delta = loading * qmax;
+    const double dg = sq[q] + delta;
+    const size_t row = size_t(f) * size_t(S) + size_t(q);
+    diag[row] = dg == 0.0 ? 1.0 : dg;
+    beam_exp[row] = alive ? row_exponent(sumtop / (delta > 0.0 ? delta : qmax)) : 0;
+    beam_live[row] = alive && sq[q] > 0.0 ? 1 : 0;
+  }
+}
+
+// The null-steering beams (beamform.py, separate): Z[f,:,k] = (G + delta I)^-1 Y with Y as k_steer_sum forms it (weights = gains, the
+// same operations in the same order, all S <= ST beams in one pass) and G[s,t] = sum_m (g[s,m] g[t,m]) p[s,m] conj(p[t,m]), t < s, the
+// Gram matrix of the steering vectors.  The launch shape, the LDS tiles and the load ahead are k_steer_sum's; every (s, m) phase is
+// evaluated once and updates Y[s] and the row and column s of G's lower triangle, all in registers: ST (ST - 1) / 2 + ST complex
+// accumulators per lane.  After the loop the lane factors and solves in registers (separate_math.h holds the operation order) with
+// the frame's loaded diagonal, exponent and live marks from k_separate_frame: they are uniform over the grid's row, so they cost the
+// lanes no registers and no work per microphone.
+template <int ST>
+__global__ __launch_bounds__(256) void k_separate(const cd* __restrict__ X, const double* __restrict__ delays, const double* __restrict__ gains,
+                                                  int M, int N, int S, double val, const double* __restrict__ diag,
+                                                  const int* __restrict__ beam_exp, const int* __restrict__ beam_live, cd* __restrict__ Z) {
+  constexpr int NT = sep_tri_count(ST);
+  __shared__ double sd[ST][kSteerMics], sw[ST][kSteerMics];
+  const int H = N + 1, f = blockIdx.y, tid = threadIdx.x, ns = S;
+  const int k = blockIdx.x * kSteerBins + tid;
+  const bool in_row = k < H;
+  const int kk = in_row ? k : H - 1;                          // lanes past the row compute bin N again and store nothing
+  const double fk = kk == N ? -double(N) * val : double(kk) * val;   // fftfreq: bin N carries -fs/2
+  const double a = -6.283185307179586 * fk;
+  const cd* x = X + size_t(f) * size_t(M) * size_t(H) + size_t(kk);
+  double ax[ST], ay[ST], gre[NT + 1], gim[NT + 1];
+#pragma unroll
+  for (int q = 0; q < ST; ++q) ax[q] = ay[q] = 0.0;
+#pragma unroll
+  for (int q = 0; q < NT + 1; ++q) gre[q] = gim[q] = 0.0;
+  for (int m0 = 0; m0 < M; m0 += kSteerMics) {
+    const int mt = M - m0 < kSteerMics ? M - m0 : kSteerMics;
+    __syncthreads();                                          // the previous tile has been read
+    for (int i = tid; i < ST * kSteerMics; i += kSteerBins) {
+      const int q = i / kSteerMics, m = i % kSteerMics;
+      const bool on = q < ns && m < mt;
+      const size_t at = (size_t(f) * size_t(S) + size_t(on ? q : 0)) * size_t(M) + size_t(m0 + (on ? m : 0));
+      sd[q][m] = on ? delays[at] : 0.0;
+      sw[q][m] = on ? gains[at] : 0.0;
+    }
+    __syncthreads();
+    cd nxt = x[size_t(m0) * size_t(H)];
+    for (int m = 0; m < mt; ++m) {
+      const cd xv = nxt;
+      if (m + 1 < mt) nxt = x[size_t(m0 + m + 1) * size_t(H)];
+      cd ph[ST];
+#pragma unroll
+      for (int q = 0; q < ST; ++q) {
+        if (q < ns) {                                         // (uniform)
+          double s, c;
+          sincos(a * sd[q][m], &s, &c);
+          ph[q] = mk(c, s);
+          const cd t = cmul(xv, ph[q]);
+          const double w = sw[q][m];
+          ax[q] = ax[q] + w * t.x;
+          ay[q] = ay[q] + w * t.y;
+        }
+      }
+#pragma unroll
+      for (int s = 1; s < ST; ++s) {
+        if (s < ns) {
+#pragma unroll
+          for (int t = 0; t < s; ++t) {
+            const double gg = sw[s][m] * sw[t][m];
+            const cd c = cmulc(ph[s], ph[t]);
+            gre[sep_tri(s, t)] = gre[sep_tri(s, t)] + gg * c.x;
+            gim[sep_tri(s, t)] = gim[sep_tri(s, t)] + gg * c.y;
+          }
+        }
+      }
+    }
+  }
+  const size_t row0 = size_t(f) * size_t(S);
+  const int e = beam_exp[row0];
+  bool alive = false;                                         // (uniform: the marks are the frame's)
+#pragma unroll
+  for (int q = 0; q < ST; ++q)
+    if (q < ns && beam_live[row0 + size_t(q)]) alive = true;
+  if (alive) {
+    double dg[ST];
+#pragma unroll
+    for (int q = 0; q < ST; ++q) dg[q] = q < ns ? diag[row0 + size_t(q)] : 1.0;
+    separate_solve<ST>(ns, dg, gre, gim, ax, ay);
+  }
+  if (in_row) {
+#pragma unroll
+    for (int q = 0; q < ST; ++q) {
+      if (q < ns) {
+        const size_t row = row0 + size_t(q);
+        Z[row * size_t(H) + size_t(k)] = beam_live[row] ? mk(ldexp(ax[q], -e), ldexp(ay[q], -e)) : mk(0, 0);
+      }
+    }
+  }
+}
+
 // the half spectra of two beams -> one complex transform of 2N points (SimLoader::operator()'s mirror and Nyquist rules)
 struct BeamLoader {
   static constexpr const char* kName = "BeamLoader";
@@ -143,6 +278,12 @@ void launch_steer_sum(dim3 grid, hipStream_t on, const cd* X, const int* flags, 
   k_steer_sum<ST><<<grid, dim3(kSteerBins), 0, on>>>(X, flags, delays, weights, M, N, S, s0, ns, val, Y, beam_exp, beam_live);
 }
 
+template <int ST>
+void launch_separate(dim3 grid, hipStream_t on, const cd* X, const double* delays, const double* gains, int M, int N, int S, double val,
+                     const double* diag, const int* beam_exp, const int* beam_live, cd* Z) {
+  k_separate<ST><<<grid, dim3(kSteerBins), 0, on>>>(X, delays, gains, M, N, S, val, diag, beam_exp, beam_live, Z);
+}
+
 }  // namespace
 
 int Engine::steer_check(int B, int M, int L, double fs, int S) {
@@ -154,11 +295,33 @@ int Engine::steer_check(int B, int M, int L, double fs, int S) {
   return PAL_OK;
 }
 
+int Engine::separate_check(int B, int M, int L, double fs, int S, double loading) {
+  PAL_TRY(steer_check(B, M, L, fs, S));
+  if (!std::isfinite(loading) || loading < 0) return fail(PAL_ERR_INVALID, "loading must be finite and >= 0");
+  if (loading == 0 && S > 1) return fail(PAL_ERR_INVALID, "loading 0 with %d sources: bin 0 of the Gram matrix is singular", S);
+  if (S > kSeparateMax) return fail(PAL_ERR_UNSUPPORTED, "%d sources per frame exceed %d (one solve cannot be split over passes)", S, kSeparateMax);
+  return PAL_OK;
+}
+
 int Engine::steer_sum_dev(const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_weights, int S,
                           double* d_out) {
-  Engine* e = this;
   if (!d_frames || !d_delays || !d_weights || !d_out) return fail(PAL_ERR_INVALID, "NULL buffer");
   PAL_TRY(steer_check(B, M, L, fs, S));
+  return beams_dev(d_frames, B, M, L, fs, d_delays, d_weights, S, d_out, false, 0.0);
+}
+
+int Engine::separate_dev(const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_gains, int S,
+                         double loading, double* d_out) {
+  if (!d_frames || !d_delays || !d_gains || !d_out) return fail(PAL_ERR_INVALID, "NULL buffer");
+  PAL_TRY(separate_check(B, M, L, fs, S, loading));
+  return beams_dev(d_frames, B, M, L, fs, d_delays, d_gains, S, d_out, true, loading);
+}
+
+// what the two beamformers share: the table check, the slices of whole frames, the forward spectra, the beam spectra (k_steer_sum, or
+// k_separate with `solve`), the packed inverse and the dead rows
+int Engine::beams_dev(const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_weights, int S,
+                      double* d_out, bool solve, double loading) {
+  Engine* e = this;
   Plan* pl = nullptr;
   PAL_TRY(get_plan(2 * L, L, L, &pl));
   if (pfa_forward_applies(*pl, L)) return fail(PAL_ERR_INTERNAL, "packed forward transform on a steering plan");
@@ -180,6 +343,7 @@ int Engine::steer_sum_dev(const double* d_frames, int B, int M, int L, double fs
   const size_t off_flags = cv.take(size_t(F0) * M * sizeof(int));
   const size_t off_exp = cv.take(size_t(F0) * S * sizeof(int));
   const size_t off_live = cv.take(size_t(F0) * S * sizeof(int));
+  const size_t off_diag = solve ? cv.take(size_t(F0) * S * sizeof(double)) : 0;   // (last: the delay-and-sum layout is what it was)
   char* blk = nullptr;
   PAL_TRY(scratch(kWsBeam, cv.off, &blk));
   cd* X = reinterpret_cast<cd*>(blk + off_x);
@@ -187,6 +351,7 @@ int Engine::steer_sum_dev(const double* d_frames, int B, int M, int L, double fs
   int* flags = reinterpret_cast<int*>(blk + off_flags);
   int* beam_exp = reinterpret_cast<int*>(blk + off_exp);
   int* beam_live = reinterpret_cast<int*>(blk + off_live);
+  double* diag = reinterpret_cast<double*>(blk + off_diag);
   const Conv& c = pl->inv;
   const int fl = int(0.01 * double(L));
   const double d = 1.0 / fs;
@@ -199,9 +364,17 @@ int Engine::steer_sum_dev(const double* d_frames, int B, int M, int L, double fs
     }
     const double* dl = d_delays + size_t(f0) * S * M;
     const double* wt = d_weights + size_t(f0) * S * M;
-    {
+    const dim3 grid(unsigned((H + kSteerBins - 1) / kSteerBins), unsigned(F));
+    if (solve) {
+      ProfScope ps(e, "k_separate");
+      k_separate_frame<<<dim3(unsigned(F)), dim3(64), 0, stream>>>(flags, wt, M, S, loading, diag, beam_exp, beam_live);
+      PAL_TRY(check(hipGetLastError(), "k_separate_frame"));
+      if (S == 1) launch_separate<1>(grid, stream, X, dl, wt, M, L, S, val, diag, beam_exp, beam_live, Y);
+      else if (S == 2) launch_separate<2>(grid, stream, X, dl, wt, M, L, S, val, diag, beam_exp, beam_live, Y);
+      else if (S <= 4) launch_separate<4>(grid, stream, X, dl, wt, M, L, S, val, diag, beam_exp, beam_live, Y);
+      else launch_separate<8>(grid, stream, X, dl, wt, M, L, S, val, diag, beam_exp, beam_live, Y);
+    } else {
       ProfScope ps(e, "k_steer_sum");
-      const dim3 grid(unsigned((H + kSteerBins - 1) / kSteerBins), unsigned(F));
       for (int s0 = 0; s0 < S; s0 += kSteerMaxTile) {
         const int ns = S - s0 < kSteerMaxTile ? S - s0 : kSteerMaxTile;
         if (ns == 1) launch_steer_sum<1>(grid, stream, X, flags, dl, wt, M, L, S, s0, ns, val, Y, beam_exp, beam_live);
@@ -210,7 +383,7 @@ int Engine::steer_sum_dev(const double* d_frames, int B, int M, int L, double fs
         else launch_steer_sum<8>(grid, stream, X, flags, dl, wt, M, L, S, s0, ns, val, Y, beam_exp, beam_live);
       }
     }
-    PAL_TRY(check(hipGetLastError(), "k_steer_sum"));
+    PAL_TRY(check(hipGetLastError(), solve ? "k_separate" : "k_steer_sum"));
     const int rows = F * S;
     double* out = d_out + size_t(f0) * S * L;
     cd* W = nullptr;
@@ -247,6 +420,15 @@ using namespace pal;
 #define UP(dst, src, bytes) PAL_TRY(e->check(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, e->stream), "upload"))
 #define DOWN(dst, src, bytes) PAL_TRY(e->check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream), "download"))
 
+// the host forms check the tables as the device does: refused here before anything is uploaded
+static int check_steer_tables(Engine* e, const double* delays, const double* weights, size_t ntab, double fs, int L) {
+  for (size_t i = 0; i < ntab; ++i) {
+    if (!std::isfinite(delays[i]) || !std::isfinite(weights[i])) return e->fail(PAL_ERR_INVALID, "a steering delay or weight is not finite");
+    if (std::fabs(delays[i]) * fs > double(L)) return e->fail(PAL_ERR_INVALID, "a steering delay lies beyond the frame (|delay| fs > %d)", L);
+  }
+  return PAL_OK;
+}
+
 extern "C" {
 
 int pal_steer_sum_dev(pal_handle h, const double* d_frames, int B, int M, int L, double fs, const double* d_delays,
@@ -261,10 +443,7 @@ int pal_steer_sum(pal_handle h, const double* frames, int B, int M, int L, doubl
   if (!frames || !delays || !weights || !out) return e->fail(PAL_ERR_INVALID, "NULL buffer");
   PAL_TRY(e->steer_check(B, M, L, fs, S));
   const size_t nin = size_t(B) * M * L, ntab = size_t(B) * S * M, nout = size_t(B) * S * L;
-  for (size_t i = 0; i < ntab; ++i) {                       // (the device checks the same: refused here before anything is uploaded)
-    if (!std::isfinite(delays[i]) || !std::isfinite(weights[i])) return e->fail(PAL_ERR_INVALID, "a steering delay or weight is not finite");
-    if (std::fabs(delays[i]) * fs > double(L)) return e->fail(PAL_ERR_INVALID, "a steering delay lies beyond the frame (|delay| fs > %d)", L);
-  }
+  PAL_TRY(check_steer_tables(e, delays, weights, ntab, fs, L));
   double *dx = nullptr, *dt = nullptr, *dout = nullptr;
   PAL_TRY(e->scratch(kWsStageIn, nin * sizeof(double), &dx));
   PAL_TRY(e->scratch(kWsStageTable, 2 * ntab * sizeof(double), &dt));
@@ -274,6 +453,32 @@ int pal_steer_sum(pal_handle h, const double* frames, int B, int M, int L, doubl
   UP(dt + ntab, weights, ntab * sizeof(double));
   PAL_TRY(e->check(hipStreamSynchronize(e->stream), "upload sync"));
   PAL_TRY(e->steer_sum_dev(dx, B, M, L, fs, dt, dt + ntab, S, dout));
+  DOWN(out, dout, nout * sizeof(double));
+  return pal_synchronize(h);
+}
+
+int pal_separate_dev(pal_handle h, const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_gains,
+                     int S, double loading, double* d_out) {
+  ENGINE(h);
+  return e->separate_dev(d_frames, B, M, L, fs, d_delays, d_gains, S, loading, d_out);
+}
+
+int pal_separate(pal_handle h, const double* frames, int B, int M, int L, double fs, const double* delays, const double* gains, int S,
+                 double loading, double* out) {
+  ENGINE(h);
+  if (!frames || !delays || !gains || !out) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  PAL_TRY(e->separate_check(B, M, L, fs, S, loading));
+  PAL_TRY(check_steer_tables(e, delays, gains, size_t(B) * S * M, fs, L));
+  const size_t nin = size_t(B) * M * L, ntab = size_t(B) * S * M, nout = size_t(B) * S * L;
+  double *dx = nullptr, *dt = nullptr, *dout = nullptr;
+  PAL_TRY(e->scratch(kWsStageIn, nin * sizeof(double), &dx));
+  PAL_TRY(e->scratch(kWsStageTable, 2 * ntab * sizeof(double), &dt));
+  PAL_TRY(e->scratch(kWsStageOut, nout * sizeof(double), &dout));
+  UP(dx, frames, nin * sizeof(double));
+  UP(dt, delays, ntab * sizeof(double));
+  UP(dt + ntab, gains, ntab * sizeof(double));
+  PAL_TRY(e->check(hipStreamSynchronize(e->stream), "upload sync"));
+  PAL_TRY(e->separate_dev(dx, B, M, L, fs, dt, dt + ntab, S, loading, dout));
   DOWN(out, dout, nout * sizeof(double));
   return pal_synchronize(h);
 }

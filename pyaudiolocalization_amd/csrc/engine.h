@@ -282,7 +282,13 @@ struct Engine {
   int steer_check(int B, int M, int L, double fs, int S);
   int steer_sum_dev(const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_weights, int S,
                     double* d_out);
-  int beam_slice = 0;              // PAL_BEAM_SLICE=<frames>: frames per slice of steer_sum_dev (0: as many as keep the slice's spectra near 1 GiB)
+  // the null-steering beams of the same inputs (beamform.py, separate): S <= 8, loading >= 0 and > 0 where S > 1
+  int separate_check(int B, int M, int L, double fs, int S, double loading);
+  int separate_dev(const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_gains, int S,
+                   double loading, double* d_out);
+  int beams_dev(const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_weights, int S,
+                double* d_out, bool solve, double loading);
+  int beam_slice = 0;              // PAL_BEAM_SLICE=<frames>: frames per slice of steer_sum_dev and separate_dev (0: as many as keep the slice's spectra near 1 GiB)
   int32_t* solve_idx = nullptr;    // device table pair -> i | j << 16 of the last microphone count
   int solve_idx_M = 0;
   // resample.hip: the right wing of the interpolation filter as pal_resample_set_filter received it, and the ratio whose scaled

@@ -729,9 +729,9 @@ class Engine:
                                                    out.ctypes.data))
         return out[0] if one else out
 
-    def steer(self, frames, fs, delays, weights=None) -> np.ndarray:
-        """Delay-and-sum beams: frames[B][M][L], delays[B][S][M] (seconds) and weights[B][S][M] (None: 1/M) -> out[B][S][L]
-        (rule: beamform.steer).  frames[M][L] with delays[S][M] gives out[S][L]."""
+    @staticmethod
+    def _steer_tables(frames, delays, weights, default):
+        """what steer and separate do to their arrays: -> x[B][M][L], d[B][S][M], w[B][S][M] (``default(m)`` where weights is None), one"""
         x, d = f64(frames), f64(delays)
         one = x.ndim == 2 and d.ndim == 2
         if one:
@@ -739,23 +739,49 @@ class Engine:
         if x.ndim != 3 or d.ndim != 3 or d.shape[0] != x.shape[0] or d.shape[2] != x.shape[1]:
             raise ValueError("frames must be [B][M][L] with delays[B][S][M] (or [M][L] with [S][M])")
         b, m, length = x.shape
-        s = d.shape[1]
         if weights is None:
-            w = np.full(d.shape, 1.0 / m if m else 0.0)
+            w = np.full(d.shape, default(m))
         else:
             w = f64(weights)
             if one and w.ndim == 2:
                 w = w[None]
             if w.shape != d.shape:
                 raise ValueError("weights must have the shape of delays")
-        if m < 1 or s < 1 or b < 1:
+        if m < 1 or d.shape[1] < 1 or b < 1:
             raise ValueError("need at least one frame, one microphone and one steering point")
         if length < 100:
             raise ValueError("steering needs at least 100 samples (the fade window of fractional_delay)")
+        return x, d, w, one
+
+    def steer(self, frames, fs, delays, weights=None) -> np.ndarray:
+        """Delay-and-sum beams: frames[B][M][L], delays[B][S][M] (seconds) and weights[B][S][M] (None: 1/M) -> out[B][S][L]
+        (rule: beamform.steer).  frames[M][L] with delays[S][M] gives out[S][L]."""
+        x, d, w, one = self._steer_tables(frames, delays, weights, lambda m: 1.0 / m if m else 0.0)
+        b, m, length = x.shape
+        s = d.shape[1]
         out = np.empty((b, s, length))
         self._check(self._lib.pal_steer_sum(self._h, x.ctypes.data, b, m, length, float(fs), d.ctypes.data, w.ctypes.data, s,
                                             out.ctypes.data))
         return out[0] if one else out
+
+    def separate(self, frames, fs, delays, gains=None, loading=0.01) -> np.ndarray:
+        """Null-steering beams: frames[B][M][L], delays[B][S][M] (seconds) and gains[B][S][M] (None: 1) -> out[B][S][L], every beam
+        with the other S - 1 sources cancelled (rule: beamform.separate).  S <= 8; loading >= 0, and > 0 where S > 1.  frames[M][L]
+        with delays[S][M] gives out[S][L]."""
+        x, d, g, one = self._steer_tables(frames, delays, gains, lambda m: 1.0)
+        b, m, length = x.shape
+        s = d.shape[1]
+        out = np.empty((b, s, length))
+        self._check(self._lib.pal_separate(self._h, x.ctypes.data, b, m, length, float(fs), d.ctypes.data, g.ctypes.data, s, float(loading),
+                                           out.ctypes.data))
+        return out[0] if one else out
+
+    def separate_dev(self, d_frames: int, b: int, m: int, length: int, fs: float, d_delays: int, d_gains: int, s: int, loading: float,
+                     d_out: int) -> None:
+        """Engine.separate on buffers in HBM: d_frames[b][m][length], d_delays / d_gains[b][s][m] -> d_out[b][s][length]; asynchronous,
+        refused table entries and non-finite samples surface in synchronize()."""
+        self._check(self._lib.pal_separate_dev(self._h, C.c_void_p(d_frames), int(b), int(m), int(length), float(fs), C.c_void_p(d_delays),
+                                               C.c_void_p(d_gains), int(s), float(loading), C.c_void_p(d_out)))
 
     def steer_dev(self, d_frames: int, b: int, m: int, length: int, fs: float, d_delays: int, d_weights: int, s: int, d_out: int) -> None:
         """Engine.steer on buffers in HBM: d_frames[b][m][length], d_delays / d_weights[b][s][m] -> d_out[b][s][length]; asynchronous,

@@ -285,17 +285,13 @@ def srp_directions_device(frames, mic_positions, fs, c, n_az=72, n_el=36, W=2, K
     return (peaks[0], zoomed[0]) if one else (peaks, zoomed)
 
 
-def beamform_device(frames, mic_positions, fs, c, points=None, directions=None, weights=None, calib_delays=None, engine=None):
-    """frames[B][M][L] (or [M][L]) -> out[B][S][L] (or [S][L]): every frame's delay-and-sum beams at ``points`` or ``directions``
-    (exactly one of them; Engine.steer, rule: beamform.py).  Either is [B][S][3], or [S][3] for every frame, or an array of
-    _ffi.SRP_PEAK / _ffi.SRP_ZOOM records, so the peaks or the zoom results of srp_positions_device and srp_directions_device go in as
-    they are: steering at peaks 0 and 1 is what separates two sources.  An absent record or a point with a non-finite coordinate
-    gives a row of zeros.  ``weights``: [B][S][M] (or what broadcasts to it), by default 1/M.  ``calib_delays``: the per-microphone
-    calibration delays localize_sound_source corrects the pair delays with."""
+def _beam_tables(frames, mic_positions, c, points, directions, weights, calib_delays, default):
+    """The input handling beamform_device and separate_device share: -> x[B][M][L], delays[B][S][M], w[B][S][M], one.  ``points`` or
+    ``directions`` (exactly one) is [B][S][3], or [S][3] for every frame, or SRP records; ``weights`` is what broadcasts to [B][S][M], or
+    None for ``default`` everywhere (None: 1/M); a point that is not valid (absent record, non-finite coordinate) gets weights of 0."""
     from . import beamform
     if (points is None) == (directions is None):
         raise ValueError("give exactly one of points and directions")
-    eng = engine or default_engine()
     x = np.ascontiguousarray(frames, dtype=np.float64)
     one = x.ndim == 2
     if one:
@@ -320,9 +316,33 @@ def beamform_device(frames, mic_positions, fs, c, points=None, directions=None, 
     delays, valid = to_delays(where, mics, c, calib_delays)
     if weights is None:
         w = beamform.uniform_weights(valid, x.shape[1])
+        if default is not None:
+            w = np.where(valid[..., None], float(default), 0.0) * np.ones(x.shape[1])
     else:
         w = np.where(valid[..., None], np.broadcast_to(np.asarray(weights, dtype=np.float64), delays.shape), 0.0)
-    out = eng.steer(x, fs, delays, w)
+    return x, delays, w, one
+
+
+def beamform_device(frames, mic_positions, fs, c, points=None, directions=None, weights=None, calib_delays=None, engine=None):
+    """frames[B][M][L] (or [M][L]) -> out[B][S][L] (or [S][L]): every frame's delay-and-sum beams at ``points`` or ``directions``
+    (exactly one of them; Engine.steer, rule: beamform.py).  Either is [B][S][3], or [S][3] for every frame, or an array of
+    _ffi.SRP_PEAK / _ffi.SRP_ZOOM records, so the peaks or the zoom results of srp_positions_device and srp_directions_device go in as
+    they are.  An absent record or a point with a non-finite coordinate gives a row of zeros.  ``weights``: [B][S][M] (or what
+    broadcasts to it), by default 1/M.  ``calib_delays``: the per-microphone calibration delays localize_sound_source corrects the
+    pair delays with.  A beam at source 0 still holds source 1 at the level of the array's side lobes: separate_device cancels it."""
+    x, delays, w, one = _beam_tables(frames, mic_positions, c, points, directions, weights, calib_delays, None)
+    out = (engine or default_engine()).steer(x, fs, delays, w)
+    return out[0] if one else out
+
+
+def separate_device(frames, mic_positions, fs, c, points=None, directions=None, gains=None, loading=0.01, calib_delays=None, engine=None):
+    """frames[B][M][L] (or [M][L]) -> out[B][S][L] (or [S][L]): every frame's null-steering beams at ``points`` or ``directions``, the
+    inputs of beamform_device (Engine.separate, rule: beamform.separate): beam s holds source s with the other S - 1 cancelled, which
+    is what separates the sources srp_positions_device(K=2, zoom=...) finds.  ``gains``: [B][S][M] (or what broadcasts to it), by
+    default 1; an absent record or a point with a non-finite coordinate gets gains of 0, a row of zeros that the other beams do not
+    notice.  ``loading``: the diagonal loading relative to the largest sum_m gains^2 (> 0 where S > 1).  S <= 8."""
+    x, delays, g, one = _beam_tables(frames, mic_positions, c, points, directions, gains, calib_delays, 1.0)
+    out = (engine or default_engine()).separate(x, fs, delays, g, loading)
     return out[0] if one else out
 
 

@@ -1,7 +1,7 @@
 // Host checks of csrc/plan_geometry.h: the plans the GPU tests pin, the invariants of every frame length up to 2^20 under every
 // plan switch, equality with a table recorded from the device (tests/golden/plan_table.json, flattened by the Python side into
-// lines "<set> <L> n conv_len m1 m2 n1 n2 tile_len"), and length -> plan -> pair_route() for the routes
-// tests/test_gpu_peak_positions.py expects.  Built and run by tests/test_host_plan_geometry.py (no GPU needed):
+// lines "<set> <L> n conv_len m1 m2 n1 n2 tile_len"), the Rader, row and column tables of the N1 x 991 family of
+// tests/rader_family.py, and length -> plan -> pair_route() for the routes tests/test_gpu_peak_positions.py expects.  Built and run by tests/test_host_plan_geometry.py (no GPU needed):
 //   hipcc -O2 -I pyaudiolocalization_amd/csrc tests/host/test_plan_geometry.cpp -o /tmp/test_plan_geometry
 #include <cstdio>
 #include <cstring>
@@ -45,6 +45,11 @@ static PlanSwitches switches(const std::string& name) {
 static const char* kSets[] = {"default", "PAL_RADIX3=0", "PAL_FOUR_REG=0", "PAL_PFA_BIG=0", "PAL_RADER=0", "PAL_PFA=0", "PAL_R89=0"};
 
 // ---- (a) the values the GPU tests assert from the device ----
+struct RaderCase { int n1, L, nch; };
+static const RaderCase kRaderFamily[] = {{3, 1487, 1}, {9, 4460, 1}, {11, 5451, 1}, {23, 11397, 1}, {25, 12388, 2}, {45, 22298, 2}, {47, 23289, 3},
+                                         {67, 33199, 3}, {69, 34190, 4}, {87, 43109, 4}, {91, 45091, 5}, {97, 48064, 5}, {113, 55992, 6},
+                                         {127, 62929, 6}};
+
 static void check_pins() {
   const PlanSwitches def;
   struct Cut { int L, n1, n2, tile; };   // tile 0: not pinned
@@ -58,6 +63,19 @@ static void check_pins() {
     CHECK(p.ok && p.cut.n1 == c.n1 && p.cut.n2 == c.n2, "L = %d: cut %d x %d, pinned %d x %d", c.L, p.cut.n1, p.cut.n2, c.n1, c.n2);
     if (c.tile) CHECK(tile_len(p.cut) == c.tile, "L = %d: tile %d, pinned %d", c.L, tile_len(p.cut), c.tile);
     if (c.n1) CHECK((long long)c.n1 * c.n2 == p.n, "L = %d: %d x %d is not n", c.L, c.n1, c.n2);
+  }
+  // the Rader-row family (tests/rader_family.py): L = (991 N1 + 1) / 2, the smallest N1 of every class of the column passes
+  for (const RaderCase& c : kRaderFamily) {
+    const HostPlan p = plan_of(c.L, def);
+    CHECK(2 * c.L - 1 == c.n1 * kRaderPrime, "L = %d is not (991 x %d + 1) / 2", c.L, c.n1);
+    CHECK(p.ok && p.cut.n1 == c.n1 && p.cut.n2 == kRaderPrime && p.cut.rader && tile_len(p.cut) == kRaderPrime - 1 && p.cut.nch == c.nch,
+          "L = %d: cut %d x %d, rader %d, tile %d, %d chunks; pinned %d x 991, %d chunks", c.L, p.cut.n1, p.cut.n2, int(p.cut.rader),
+          tile_len(p.cut), p.cut.nch, c.n1, c.nch);
+    CHECK(p.cut.r89 == false, "L = %d: Rader-89 columns", c.L);
+  }
+  {   // 92 163 = 93 x 991 = 31 x 2973: the model prefers the shorter columns, so a padded length between two of the family's is not a Rader plan
+    const HostPlan p = plan_of(46082, def);
+    CHECK(p.ok && p.cut.n1 == 31 && p.cut.n2 == 2973 && !p.cut.rader, "L = 46082: cut %d x %d, rader %d", p.cut.n1, p.cut.n2, int(p.cut.rader));
   }
   PlanSwitches norader;
   norader.allow_rader = false;
@@ -166,13 +184,52 @@ static void check_rader_tables() {
   }
   CHECK(ix.qidx[0] == L, "qidx[0] = %d", ix.qidx[0]);
   // the kernel spectrum of a Rader convolution has unit-modulus bins apart from the first (|sum of all roots but 1| = 1): scaled 1 / (L n), 1 / L
-  const long long n = 88199;
-  const RaderSpectra sp = rader_spectra(p, n, inv_mod(89, p), ix.gpow);
-  CHECK(int(sp.inv.size()) == L && int(sp.fwd.size()) == L, "spectra");
-  for (int k = 0; k < L && !failures; ++k) {
-    const double want = k ? std::sqrt(double(p)) : 1.0;
-    CHECK(std::fabs(std::hypot(sp.fwd[k].re, sp.fwd[k].im) * L - want) <= 1e-12 * want, "forward bin %d", k);
-    CHECK(std::fabs(std::hypot(sp.inv[k].re, sp.inv[k].im) * L * double(n) - want) <= 1e-12 * want, "inverse bin %d", k);
+  std::vector<int> family{89};
+  for (const RaderCase& c : kRaderFamily) family.push_back(c.n1);
+  for (int n1 : family) {
+    const long long n = (long long)n1 * p, u2 = inv_mod(n1, p);
+    CHECK(u2 > 0 && u2 < p && u2 * n1 % p == 1, "N1 = %d: u2 = %lld", n1, u2);
+    const RaderSpectra sp = rader_spectra(p, n, u2, ix.gpow);
+    CHECK(int(sp.inv.size()) == L && int(sp.fwd.size()) == L, "N1 = %d: spectra", n1);
+    for (int k = 0; k < L && !failures; ++k) {
+      const double want = k ? std::sqrt(double(p)) : 1.0;
+      CHECK(std::fabs(std::hypot(sp.fwd[k].re, sp.fwd[k].im) * L - want) <= 1e-12 * want, "N1 = %d: forward bin %d", n1, k);
+      CHECK(std::fabs(std::hypot(sp.inv[k].re, sp.inv[k].im) * L * double(n) - want) <= 1e-12 * want, "N1 = %d: inverse bin %d", n1, k);
+      // position 0 is the plain sum of the sequence in both directions: all roots but 1, which is -1
+      if (!k) CHECK(std::fabs(sp.fwd[0].re * L + 1.0) <= 1e-12 && std::fabs(sp.fwd[0].im * L) <= 1e-12 && std::fabs(sp.inv[0].re * L * double(n) + 1.0) <= 1e-12,
+                    "N1 = %d: bin 0 is not -1", n1);
+    }
+    // what the engine hands over: the cut's u2 is made even (the chirp of the non-Rader tiles needs it), build_pfa() passes u2 mod N2
+    const HostPlan hp = plan_of(int((n + 1) / 2), PlanSwitches());
+    CHECK(hp.ok && hp.cut.n1 == n1 && (hp.cut.u2 & 1) == 0 && hp.cut.u2 % p == u2 && hp.cut.u2 < 2 * p, "N1 = %d: the cut's u2 = %lld, N1^-1 = %lld", n1, hp.cut.u2, u2);
+    CHECK(hp.cut.u1 == int(inv_mod(p, n1)) && (long long)hp.cut.u1 * p % n1 == 1 % n1, "N1 = %d: u1 = %d", n1, hp.cut.u1);
+    if (failures) return;
+    // row table: per row k the twiddle index multiplier u1 k mod N1 and its step 2^last_lp times that
+    for (int lp : {0, 7}) {
+      const std::vector<RowStep> rows = pfa_row_table(n1, hp.cut.u1, lp);
+      CHECK(int(rows.size()) == n1, "N1 = %d: %zu rows in the row table", n1, rows.size());
+      for (int k = 0; k < n1 && k < int(rows.size()); ++k)
+        CHECK(rows[k].mult == int((long long)hp.cut.u1 * k % n1) && rows[k].step == int(((long long)rows[k].mult << lp) % n1), "N1 = %d: row table at %d: %d, %d",
+              n1, k, rows[k].mult, rows[k].step);
+    }
+    // column table [h + kColUnroll steps][nch chunks][cos x kColChunk | sin x kColChunk]: cos / sin(2 pi j t / N1) at step j, output index
+    // t = chunk * kColChunk + tt + 1; zeros at every index beyond h (a last chunk that is not full) and in the kColUnroll rows behind step h
+    // (k_pfa_fwd_cols and the inverse's column kernels run whole batches of kColUnroll steps)
+    const int h = (n1 - 1) / 2, nch = hp.cut.nch;
+    const std::vector<double> tab = pfa_col_table(n1, nch);
+    CHECK(nch == (h + kColChunk - 1) / kColChunk && tab.size() == size_t(h + kColUnroll) * nch * 2 * kColChunk, "N1 = %d: column table of %zu entries", n1, tab.size());
+    if (failures) return;
+    for (int j = 1; j <= h + kColUnroll; ++j)
+      for (int ch = 0; ch < nch; ++ch)
+        for (int tt = 0; tt < kColChunk; ++tt) {
+          const double* row = &tab[(size_t(j - 1) * nch + ch) * 2 * kColChunk];
+          const int t = ch * kColChunk + tt + 1;
+          if (j > h || t > h) CHECK(row[tt] == 0.0 && row[kColChunk + tt] == 0.0, "N1 = %d: column table at step %d, index %d is not zero", n1, j, t);
+          else {
+            const double ang = 6.283185307179586 * double((long long)j * t % n1) / double(n1);   // (two roundings of an angle below 2 pi: 1.4e-15)
+            CHECK(std::fabs(row[tt] - std::cos(ang)) <= 4e-15 && std::fabs(row[kColChunk + tt] - std::sin(ang)) <= 4e-15, "N1 = %d: column table at step %d, index %d", n1, j, t);
+          }
+        }
   }
   // the column and row tables of 89 x 991
   const std::vector<double> T = pfa_col_table(89, 4);

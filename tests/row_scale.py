@@ -119,21 +119,24 @@ def oracle_table(name: str, b: int, exps: Dict[int, int], med, method: str) -> D
     return out
 
 
+def row_margin(corr: np.ndarray, length: int, fs: float, med, method: str) -> float:
+    """height of the oracle's selected peak of `corr` above the runner-up of O.select_peaks (inf: a single candidate); where
+    the oracle falls back to the argmax, the largest sample above the second largest"""
+    ks, branch = O.select_peaks(corr, length, fs, 2, method, 1.0, med)
+    top = np.sort(corr)[-2:]
+    if branch & (O.BR_ARGMAX_NO_PEAKS | O.BR_ARGMAX_WINDOW):
+        margin = float(top[1] - top[0])
+    else:
+        margin = float("inf") if ks.size < 2 else float(corr[ks[0]] - corr[ks[1]])
+    return min(margin, float(top[1] - top[0]))                      # (k_argmax is compared exactly as well)
+
+
 def peak_margin(name: str, b: int, i: int, j: int, ei: int, ej: int, med, method: str) -> float:
-    """height of the oracle's selected peak above the runner-up of O.select_peaks (inf: a single candidate); where the
-    oracle falls back to the argmax, the largest sample above the second largest"""
+    """row_margin() of the oracle row of microphones i, j of frame b scaled by 2^ei, 2^ej"""
     key = (name, b, i, j, ei, ej, med, method)
     if key not in _MARGIN:
         _, _, length, fs = PHAT_SHAPES[name]
-        corr = oracle_corr(name, b, i, j, ei, ej)
-        ks, branch = O.select_peaks(corr, length, fs, 2, method, 1.0, med)
-        if branch & (O.BR_ARGMAX_NO_PEAKS | O.BR_ARGMAX_WINDOW):
-            top = np.sort(corr)[-2:]
-            _MARGIN[key] = float(top[1] - top[0])
-        else:
-            _MARGIN[key] = float("inf") if ks.size < 2 else float(corr[ks[0]] - corr[ks[1]])
-        top = np.sort(corr)[-2:]                                    # (k_argmax is compared exactly as well)
-        _MARGIN[key] = min(_MARGIN[key], float(top[1] - top[0]))
+        _MARGIN[key] = row_margin(oracle_corr(name, b, i, j, ei, ej), length, fs, med, method)
     return _MARGIN[key]
 
 

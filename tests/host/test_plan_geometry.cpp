@@ -95,6 +95,46 @@ static void check_pins() {
     const HostPlan q = plan_of(r.L, lds);
     CHECK(q.ok && !q.inv.reg() && (1 << q.inv.l2) <= 2048, "L = %d with the register route off: rows of %d", r.L, 1 << q.inv.l2);
   }
+  // frames above 98 304 samples (tests/long_frames.py RUNGS / CUTS): both ends of every rung of the LDS-tile convolutions and the five
+  // long cuts; forward and inverse convolution under default switches and with the prime-factor route off, and the cut
+  struct G3 { ConvKind kind; int a, l2; };   // a: l1 of the LDS kinds, m1 of the register kinds
+  struct Long { int L; G3 inv, fwd; int n1, n2, lm, nch; };
+  const ConvKind kL = ConvKind::kLds, k3 = ConvKind::kLds3, k2 = ConvKind::kReg2;
+  const Long longs[] = {
+      {98305, {kL, 9, 10}, {k2, 32, 13}, 0, 0, 0, 1},   {131072, {kL, 9, 10}, {k2, 32, 13}, 73, 3591, 13, 4},
+      {131073, {k3, 8, 10}, {k2, 48, 13}, 65, 4033, 13, 3}, {196608, {k3, 8, 10}, {k2, 48, 13}, 0, 0, 0, 1},
+      {196609, {kL, 9, 11}, {kL, 9, 10}, 0, 0, 0, 1},   {262144, {kL, 9, 11}, {kL, 9, 10}, 0, 0, 0, 1},
+      {262145, {k3, 8, 11}, {k3, 8, 10}, 0, 0, 0, 1},   {393216, {k3, 8, 11}, {k3, 8, 10}, 0, 0, 0, 1},
+      {393217, {kL, 10, 11}, {kL, 9, 11}, 0, 0, 0, 1},  {524288, {kL, 10, 11}, {kL, 9, 11}, 0, 0, 0, 1},
+      {524289, {kL, 11, 11}, {k3, 8, 11}, 0, 0, 0, 1},  {786432, {kL, 11, 11}, {k3, 8, 11}, 0, 0, 0, 1},
+      {786433, {kL, 11, 11}, {kL, 10, 11}, 0, 0, 0, 1}, {1048576, {kL, 11, 11}, {kL, 10, 11}, 0, 0, 0, 1},
+      {131079, {k3, 8, 10}, {k2, 48, 13}, 119, 2203, 13, 6}, {196649, {kL, 9, 11}, {kL, 9, 10}, 93, 4229, 14, 5},
+      {520129, {kL, 10, 11}, {kL, 9, 11}, 127, 8191, 14, 6}};
+  const auto same = [](const ConvGeom& g, const G3& w) {
+    const int m1 = w.kind == ConvKind::kLds ? 1 << w.a : (w.kind == ConvKind::kLds3 ? 3 << w.a : w.a);
+    return g.kind == w.kind && g.m1 == m1 && g.l2 == w.l2 && g.l1 == (g.reg() ? 0 : w.a) && g.m == (size_t(m1) << w.l2);
+  };
+  for (const Long& c : longs) {
+    const HostPlan p = plan_of(c.L, def), q = plan_of(c.L, nopfa);
+    CHECK(p.ok && same(p.inv, c.inv) && same(p.fwd, c.fwd), "L = %d: inverse kind %d %d x 2^%d, forward kind %d %d x 2^%d", c.L, int(p.inv.kind),
+          p.inv.m1, p.inv.l2, int(p.fwd.kind), p.fwd.m1, p.fwd.l2);
+    CHECK(q.ok && same(q.inv, c.inv) && same(q.fwd, c.fwd) && q.cut.n1 == 0, "L = %d with the prime-factor route off: inverse kind %d %d x 2^%d, forward kind %d %d x 2^%d, cut %d",
+          c.L, int(q.inv.kind), q.inv.m1, q.inv.l2, int(q.fwd.kind), q.fwd.m1, q.fwd.l2, q.cut.n1);
+    CHECK(p.cut.n1 == c.n1 && p.cut.n2 == c.n2 && p.cut.lm == c.lm && p.cut.nch == c.nch && !p.cut.rader && !p.cut.r89, "L = %d: cut %d x %d, lm %d, %d chunks; pinned %d x %d, lm %d, %d chunks",
+          c.L, p.cut.n1, p.cut.n2, p.cut.lm, p.cut.nch, c.n1, c.n2, c.lm, c.nch);
+    if (c.n1) CHECK((long long)c.n1 * c.n2 == p.n && tile_len(p.cut) == (1 << c.lm) && (1 << c.lm) >= 2 * c.n2 - 1, "L = %d: %d x %d, tile %d", c.L, c.n1, c.n2, tile_len(p.cut));
+  }
+  {   // 520 129 is the longest frame that takes any cut, and its tile is the fullest (16 381 of 16 384 points)
+    for (int L = 520130; L <= (1 << 20); ++L) CHECK(plan_of(L, def).cut.n1 == 0, "L = %d takes a cut", L);
+    CHECK(2 * 8191 - 1 == 16381, "tile fill");
+  }
+  // pal_xcorr_vs_ref convolves 2 N - 1 points (tests/long_frames.py SPARSE_GEOM)
+  struct X { int N; G3 g; };
+  const X xs[] = {{196609, {kL, 9, 10}}, {262145, {k3, 8, 10}}, {393217, {kL, 9, 11}}, {524289, {k3, 8, 11}}, {1048576, {kL, 10, 11}}};
+  for (const X& x : xs) {
+    ConvGeom g;
+    CHECK(conv_geometry(2 * size_t(x.N) - 1, def, &g) && same(g, x.g), "xcorr N = %d: kind %d %d x 2^%d", x.N, int(g.kind), g.m1, g.l2);
+  }
 }
 
 // ---- (b) invariants ----

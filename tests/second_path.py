@@ -272,6 +272,26 @@ def all_xcorr_inputs():
     return count
 
 
+def check_xcorr(measured, exact, ref, n, tag):
+    """(kpk, win5, pkabs, refpk) of Engine.xcorr_vs_ref against the exact sequences of the rows: the peak index, its magnitude and the
+    five-sample window within 1e-10 max(1, peak), NaN in the window's slots outside the sequence; shared by the GPU modules"""
+    kpk, win, pk, refpk = measured
+    length = 2 * n - 1
+    for q, seq in enumerate(exact):
+        at = int(np.argmax(np.abs(seq)))
+        peak = float(abs(seq[at]))
+        tol = 1e-10 * max(1.0, peak)
+        assert int(kpk[q]) == at, (tag, q, int(kpk[q]), at)
+        assert abs(pk[q] - peak) <= tol, (tag, q)
+        for j in range(5):
+            p = at + j - 2
+            if 0 <= p < length:
+                assert abs(win[q, j] - seq[p]) <= tol, (tag, q, j, win[q, j], seq[p])
+            else:
+                assert np.isnan(win[q, j]), (tag, q, j, win[q, j])
+    assert refpk == pk[ref], tag
+
+
 # ------------------------------------------------------------------------------------------------ filter inputs and answers
 _FILT_ROWS: Dict[Tuple[str, int], np.ndarray] = {}
 _FILT_WANT: Dict[Tuple[str, int, int], np.ndarray] = {}

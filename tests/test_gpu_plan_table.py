@@ -8,7 +8,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_table.json")
-MAX_LENGTH = 100000              # longer frames only cost plan memory here; the host test compares every recorded row
+MAX_LENGTH = 1 << 20             # every recorded row (tests/test_gpu_long_frames.py builds plans of the longest frames anyway)
 
 
 def test_plan_info_equals_the_recorded_table(monkeypatch):

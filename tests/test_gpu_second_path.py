@@ -310,24 +310,6 @@ def test_simulate_multipath_refusals(engine):
 
 
 # ================================================================================================ xcorr / sync / energies
-def _check_xcorr(measured, exact, ref, n, tag):
-    kpk, win, pk, refpk = measured
-    length = 2 * n - 1
-    for q, seq in enumerate(exact):
-        at = int(np.argmax(np.abs(seq)))
-        peak = float(abs(seq[at]))
-        tol = 1e-10 * max(1.0, peak)
-        assert int(kpk[q]) == at, (tag, q, int(kpk[q]), at)
-        assert abs(pk[q] - peak) <= tol, (tag, q)
-        for j in range(5):
-            p = at + j - 2
-            if 0 <= p < length:
-                assert abs(win[q, j] - seq[p]) <= tol, (tag, q, j, win[q, j], seq[p])
-            else:
-                assert np.isnan(win[q, j]), (tag, q, j, win[q, j])
-    assert refpk == pk[ref], tag
-
-
 @pytest.mark.parametrize("n", S.XCORR_N)
 def test_xcorr_vs_ref_integer_rows(engine, n):
     """N from one sample (a correlation of one point, four NaN slots) to past a power of two; R = 1, 2, 7; the reference row
@@ -336,7 +318,7 @@ def test_xcorr_vs_ref_integer_rows(engine, n):
         case = S.xcorr_case(n, r)
         for ref in case.refs:
             measured = engine.xcorr_vs_ref(case.rows, ref)
-            _check_xcorr(measured, case.exact[ref], ref, n, (case.name, ref))
+            S.check_xcorr(measured, case.exact[ref], ref, n, (case.name, ref))
             if r == 7:
                 try:
                     engine.set_chunk(2)                              # 4 packed transforms: two launch groups, the second with row0 = 4
@@ -362,7 +344,7 @@ def test_xcorr_crafted_peaks_and_synchronize(engine, n):
     for case in S.crafted_cases(n):
         ref = case.refs[0]
         kpk, win, pk, refpk = engine.xcorr_vs_ref(case.rows, ref)
-        _check_xcorr((kpk, win, pk, refpk), case.exact[ref], ref, n, case.name)
+        S.check_xcorr((kpk, win, pk, refpk), case.exact[ref], ref, n, case.name)
         assert refpk == 16.0
         neg = 3 if "low" in case.name else 4
         assert win[neg, 2] < 0 < pk[neg] and pk[neg] == -win[neg, 2]
@@ -390,7 +372,7 @@ def test_sync_measure_dev_odd_microphone_count(engine):
         ref, kpk, win, pk, refpk = engine.sync_measure_dev(d_rows, S.SYNC_B, S.SYNC_M, S.SYNC_N)
     assert ref.tolist() == refs
     for f in range(S.SYNC_B):
-        _check_xcorr((kpk[f], win[f], pk[f], refpk[f]), exact[f], refs[f], S.SYNC_N, ("sync", f))
+        S.check_xcorr((kpk[f], win[f], pk[f], refpk[f]), exact[f], refs[f], S.SYNC_N, ("sync", f))
         alone = engine.xcorr_vs_ref(frames[f], refs[f])
         assert kpk[f].tobytes() == alone[0].tobytes() and win[f].tobytes() == alone[1].tobytes()
         assert pk[f].tobytes() == alone[2].tobytes() and refpk[f] == alone[3]

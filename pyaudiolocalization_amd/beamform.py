@@ -1,5 +1,5 @@
-"""Delay-and-sum and null-steering beamformers: the specifications of ``Engine.steer`` and ``Engine.separate`` (csrc/beamform.hip) and
-the helpers that turn positions, directions and SRP records into steering delays.  Pure NumPy, no engine call - the role closure.py,
+"""Delay-and-sum, null-steering and MVDR beamformers: the specifications of ``Engine.steer``, ``Engine.separate`` and ``Engine.mvdr``
+(csrc/beamform.hip) and the helpers that turn positions, directions and SRP records into steering delays.  Pure NumPy, no engine call - the role closure.py,
 consensus.py and srp.py play for their features.
 
 ``steer(frames[B][M][L], fs, delays[B][S][M], weights[B][S][M]) -> out[B][S][L]``::
@@ -34,6 +34,11 @@ all zero has a zero row and column in G: its output is a row of exact zeros and 
 weighted row gives S rows of exact zeros.  Two sources with the same delays do not break the solve (delta > 0 keeps the factor
 positive) and give two equal rows.  ``cond(G + delta I) <= (S + loading) / loading`` where q is equal across sources, and
 ``|(G + delta I)^-1| <= 1 / delta`` always - the bound the test tolerances rest on.
+
+``mvdr(frames[B][M][L], fs, delays[G][S][M], gains[G][S][M], loading, groups) -> out[B][S][L]`` takes the weights from the data: the
+frames are G groups of snapshots, each group's covariance per bin gives ``w = R~^-1 a / (a^H R~^-1 a)``, the beam that passes source s
+unchanged and has the least power otherwise - an interferer nobody located is cancelled where it is stationary over the group.  The
+rule stands in ``mvdr``'s docstring, its steps are ``mvdr_covariance`` and ``mvdr_weights``.
 """
 from __future__ import annotations
 
@@ -170,6 +175,146 @@ def separate(frames, fs, delays, gains, loading=0.01) -> np.ndarray:
     diag = np.where(diag == 0.0, 1.0, diag)
     z = solve_loaded(np.moveaxis(diag, 0, 1)[:, :, None], np.moveaxis(gram, 0, 2), np.moveaxis(y, 0, 1))   # [S][B][2L]
     return np.fft.ifft(np.moveaxis(z, 0, 1), axis=-1).real[..., :length] * fade_window(length)
+
+
+def check_mvdr(loading, b: int, groups: int) -> tuple[float, int]:
+    """loading finite and > 0 (with fewer snapshots than microphones it is what makes the factor exist); groups >= 1 divides b"""
+    loading = float(loading)
+    if not np.isfinite(loading) or loading <= 0:
+        raise ValueError("loading must be finite and > 0")
+    groups = int(groups)
+    if groups < 1 or b % groups:
+        raise ValueError("groups must be >= 1 and divide the number of frames")
+    return loading, groups
+
+
+def _mvdr_tables(frames, delays, gains, groups):
+    x = np.asarray(frames, dtype=np.float64)
+    d = np.asarray(delays, dtype=np.float64)
+    g = np.asarray(gains, dtype=np.float64)
+    if x.ndim != 3:
+        raise ValueError("frames must be [B][M][L]")
+    if d.ndim != 3 or d.shape != g.shape or d.shape[0] != groups or d.shape[2] != x.shape[1]:
+        raise ValueError("delays and gains must be [G][S][M] matching frames[B][M][L] in G groups")
+    return x, d, g
+
+
+def mvdr_covariance(frames, groups=1) -> np.ndarray:
+    """frames[B][M][L] in G groups of Q = B / G consecutive frames -> R[G][M][M][2L] complex: the lower triangle (j <= i) of the
+    groups' sample covariances per bin, R[i,j] = sum_b X[b,i] conj(X[b,j]) over the group's frames b ascending, the products written
+    out ((a+jb) conj(c+jd) = (ac + bd) + j(bc - ad), each bracket formed first, then added); the diagonal is real, j > i stays 0."""
+    x = np.asarray(frames, dtype=np.float64)
+    if x.ndim != 3:
+        raise ValueError("frames must be [B][M][L]")
+    b, m, length = x.shape
+    groups = int(groups)
+    if groups < 1 or b % groups:
+        raise ValueError("groups must be >= 1 and divide the number of frames")
+    q = b // groups
+    spec = np.fft.fft(x, n=2 * length, axis=-1).reshape(groups, q, m, 2 * length)
+    re, im = spec.real, spec.imag
+    rre = np.zeros((groups, m, m, 2 * length))
+    rim = np.zeros((groups, m, m, 2 * length))
+    for i in range(m):
+        for t in range(q):
+            a, bb = re[:, t, i, None], im[:, t, i, None]                        # [G][1][2L] against columns 0 .. i
+            c, dd = re[:, t, : i + 1], im[:, t, : i + 1]
+            rre[:, i, : i + 1] = rre[:, i, : i + 1] + (a * c + bb * dd)
+            rim[:, i, : i + 1] = rim[:, i, : i + 1] + (bb * c - a * dd)
+    return rre + 1j * rim
+
+
+def mvdr_weights(frames, fs, delays, gains, loading=0.1, groups=1) -> np.ndarray:
+    """frames[B][M][L], delays / gains[G][S][M] -> w[G][S][M][2L]: the MVDR weights of every group, source and bin (the rule in
+    ``mvdr``'s docstring): w = R~^-1 a / (a^H R~^-1 a) with R~ the group's covariance under the loading ``loading * tr(R) / M``."""
+    loading, groups = check_mvdr(loading, np.shape(frames)[0] if np.ndim(frames) == 3 else 0, groups)
+    x, d, g = _mvdr_tables(frames, delays, gains, groups)
+    m, length = x.shape[1], x.shape[2]
+    s = d.shape[1]
+    r = mvdr_covariance(x, groups)
+    lre = np.ascontiguousarray(np.moveaxis(r.real, 0, 2))                       # [M][M][G][2L]
+    lim = np.ascontiguousarray(np.moveaxis(r.imag, 0, 2))
+    tr = np.zeros(lre.shape[2:])
+    for i in range(m):
+        tr = tr + lre[i, i]
+    delta = loading * (tr / m)
+    rinv = np.empty((m,) + tr.shape)
+    for j in range(m):                                                          # the factor, column by column (solve_loaded's order)
+        dg = lre[j, j] + delta
+        sj = np.where(dg == 0.0, 1.0, dg)
+        for k in range(j):
+            sj = sj - (lre[j, k] * lre[j, k] + lim[j, k] * lim[j, k])
+        rinv[j] = 1.0 / np.sqrt(sj)
+        if j + 1 < m:
+            vre, vim = lre[j + 1:, j], lim[j + 1:, j]                           # rows i > j at once: each keeps its own k-ascending sum
+            for k in range(j):
+                a, b, c, dd = lre[j + 1:, k], lim[j + 1:, k], lre[j, k], lim[j, k]
+                vre = vre - (a * c + b * dd)
+                vim = vim - (b * c - a * dd)
+            lre[j + 1:, j] = vre * rinv[j]
+            lim[j + 1:, j] = vim * rinv[j]
+    f = np.fft.fftfreq(2 * length, d=1.0 / fs)
+    ure = np.empty((m, groups, s, 2 * length))
+    uim = np.empty_like(ure)
+    for i in range(m):                                                          # a, then u = L^-1 a
+        p = np.exp(-1j * 2 * np.pi * f[None, None, :] * d[:, :, i, None])       # [G][S][2L]
+        vre, vim = g[:, :, i, None] * p.real, g[:, :, i, None] * (-p.imag)      # a = gains * conj(p)
+        for k in range(i):
+            a, b, c, dd = lre[i, k][:, None], lim[i, k][:, None], ure[k], uim[k]
+            vre = vre - (a * c - b * dd)
+            vim = vim - (a * dd + b * c)
+        ure[i] = vre * rinv[i][:, None]
+        uim[i] = vim * rinv[i][:, None]
+    den = np.zeros(ure.shape[1:])
+    for i in range(m):
+        den = den + (ure[i] * ure[i] + uim[i] * uim[i])
+    den = np.where(den == 0.0, 1.0, den)
+    for i in range(m - 1, -1, -1):                                              # z = L^-H u in place
+        vre, vim = ure[i], uim[i]
+        for k in range(i + 1, m):
+            a, b, c, dd = lre[k, i][:, None], lim[k, i][:, None], ure[k], uim[k]
+            vre = vre - (a * c + b * dd)
+            vim = vim - (a * dd - b * c)
+        ure[i] = vre * rinv[i][:, None]
+        uim[i] = vim * rinv[i][:, None]
+    return np.moveaxis(ure / den + 1j * (uim / den), 0, 2)                      # [G][S][M][2L]
+
+
+def mvdr(frames, fs, delays, gains, loading=0.1, groups=1) -> np.ndarray:
+    """frames[B][M][L], delays / gains[G][S][M] -> out[B][S][L]: the minimum-variance distortionless-response beams.  B = G Q; group g
+    is the Q consecutive frames g Q .. g Q + Q - 1, the snapshots of one covariance under one steering table.  Per group and bin of
+    the 2L-point spectrum, with steer's X and f::
+
+        R[i,j]  = sum over the group's frames b ascending of  X[b,i] * conj(X[b,j])              for j <= i   (diagonal real)
+        tr      = sum over i ascending of R[i,i]
+        delta   = loading * (tr / M)                          (per bin: the weights do not depend on the data's scale)
+        diag[i] = R[i,i] + delta,  1 where that is 0          (a silent bin)
+        L       = lower Cholesky factor of (R with that diagonal), solve_loaded's column order and spelled-out products
+        a[m]    = gains[g,s,m] * conj(p[s,m]),   p[s,m] = exp(-1j*2*pi*f*delays[g,s,m])          (separate's steering vector)
+        u       = L^-1 a  (forward substitution, k ascending);   den = sum over i ascending of |u[i]|^2,  1 where that is 0
+        w       = L^-H u / den  (back substitution, k ascending)                                 (w = R~^-1 a / (a^H R~^-1 a))
+        Y[b,s]  = sum over m ascending of conj(w[m]) * X[b,m]                                    for every frame b of the group
+        out[b,s] = ifft(Y[b,s]).real[:L] * fade_window(L)
+
+    Consequences: ``w(-f) = conj(w(f))``, so L + 1 bins carry everything.  Beams and groups do not see each other.  A group scaled by a
+    power of two gives its output times that power (2^+-40: byte for byte).  A source without gains is a row of exact zeros, and so
+    is a zero frame in a live group.  ``|w|_2 <= kappa / |a|_2`` with ``kappa = M / loading + 1``, and as loading -> inf the beam
+    tends to ``steer(frames, fs, delays, gains / q)``, ``q = sum_m gains^2``, within ``2 M / loading`` of steer's scale."""
+    w = mvdr_weights(frames, fs, delays, gains, loading, groups)
+    x = np.asarray(frames, dtype=np.float64)
+    b, m, length = x.shape
+    groups = w.shape[0]
+    q = b // groups
+    spec = np.fft.fft(x, n=2 * length, axis=-1).reshape(groups, q, 1, m, 2 * length)
+    xr, xi = spec.real, spec.imag
+    wr, wi = w.real[:, None], w.imag[:, None]                                   # [G][1][S][M][2L]
+    yre = np.zeros((groups, q, w.shape[1], 2 * length))
+    yim = np.zeros_like(yre)
+    for i in range(m):
+        yre = yre + (wr[:, :, :, i] * xr[:, :, :, i] + wi[:, :, :, i] * xi[:, :, :, i])
+        yim = yim + (wr[:, :, :, i] * xi[:, :, :, i] - wi[:, :, :, i] * xr[:, :, :, i])
+    y = (yre + 1j * yim).reshape(b, w.shape[1], 2 * length)
+    return np.fft.ifft(y, axis=-1).real[..., :length] * fade_window(length)
 
 
 def _calibrated(d: np.ndarray, calib_delays) -> np.ndarray:

@@ -9,9 +9,13 @@
 // SimStorer: fade window, exponent put back).  Built with -ffp-contract=off: the operation order below is what runs.
 // The null-steering beamformer (beamform.py, separate) is the same path with k_separate_frame and k_separate in k_steer_sum's place:
 // the S beam spectra of a bin are solved against the Gram matrix of the S steering vectors, so each beam cancels the other sources.
+// The MVDR beamformer (beamform.py, mvdr; Engine::mvdr_dev below, kernels in mvdr_kernels.h) takes its weights from the covariance of
+// a group of frames: two sweeps over the group's slices with the Cholesky factor of every bin between them, the same inverse.
+#include <climits>
 #include <cmath>
 
 #include "conv_kernels.h"
+#include "mvdr_geometry.h"
 #include "reduce.h"
 #include "separate_math.h"
 #include "sim_rows.h"
@@ -272,6 +276,8 @@ __global__ __launch_bounds__(256) void k_steer_silence(double* __restrict__ out,
   for (int i = threadIdx.x; i < L; i += 256) y[i] = 0.0;
 }
 
+#include "mvdr_kernels.h"
+
 template <int ST>
 void launch_steer_sum(dim3 grid, hipStream_t on, const cd* X, const int* flags, const double* delays, const double* weights, int M, int N,
                       int S, int s0, int ns, double val, cd* Y, int* beam_exp, int* beam_live) {
@@ -408,6 +414,129 @@ int Engine::beams_dev(const double* d_frames, int B, int M, int L, double fs, co
   return PAL_OK;
 }
 
+int Engine::mvdr_check(int B, int M, int L, double fs, int G, int S, double loading) {
+  PAL_TRY(steer_check(B, M, L, fs, S));
+  if (G < 1 || B % G != 0) return fail(PAL_ERR_INVALID, "the %d frames do not split into %d groups", B, G);
+  if (!std::isfinite(loading) || !(loading > 0)) return fail(PAL_ERR_INVALID, "loading must be finite and > 0");
+  if (M > kMvdrMaxMics) return fail(PAL_ERR_UNSUPPORTED, "%d microphones exceed %d (one wavefront factors a bin)", M, kMvdrMaxMics);
+  if (mvdr_unsupported(M, size_t(L) + 1))
+    return fail(PAL_ERR_UNSUPPORTED, "the covariance triangle of %d microphones at %d samples exceeds %llu bytes", M, L,
+                (unsigned long long)kMvdrTriangleBound);
+  if ((S + 3) / 4 > 65535) return fail(PAL_ERR_UNSUPPORTED, "too many sources");
+  return PAL_OK;
+}
+
+// MVDR beams (beamform.py, mvdr): per group of Q = B / G frames, sweep 1 adds every slice's spectra into the covariance triangle,
+// k_mvdr_weights turns the triangle into W[s][m][H], sweep 2 applies W to every slice's spectra (kept where the group is one slice,
+// formed again otherwise) and sends the rows through beams_dev's inverse.  Slices hold whole frames of one group.
+int Engine::mvdr_dev(const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_gains, int G, int S,
+                     double loading, double* d_out, double* d_weights) {
+  if (!d_frames || !d_delays || !d_gains || !d_out) return fail(PAL_ERR_INVALID, "NULL buffer");
+  PAL_TRY(mvdr_check(B, M, L, fs, G, S, loading));
+  Engine* e = this;
+  Plan* pl = nullptr;
+  PAL_TRY(get_plan(2 * L, L, L, &pl));
+  if (pfa_forward_applies(*pl, L)) return fail(PAL_ERR_INTERNAL, "packed forward transform on a steering plan");
+  int* status = nullptr;
+  PAL_TRY(status_words(&status));
+  const size_t ntab = size_t(G) * size_t(S) * size_t(M);
+  k_steer_check<<<dim3(unsigned((ntab + 255) / 256)), dim3(256), 0, stream>>>(d_delays, d_gains, ntab, fs, double(L), status);
+  PAL_TRY(check(hipGetLastError(), "k_steer_check"));
+  const size_t H = size_t(pl->H);
+  const int Q = B / G;
+  const int F0 = mvdr_slice_frames(M, H, beam_slice, Q);
+  const int nsl = mvdr_slice_count(Q, F0);
+  const size_t wbytes = size_t(S) * M * H * sizeof(cd);
+  Carve cv;
+  const size_t off_x = cv.take(size_t(F0) * M * H * sizeof(cd));
+  const size_t off_y = cv.take(size_t(F0) * S * H * sizeof(cd));
+  const size_t off_flags = cv.take(size_t(F0) * M * sizeof(int));
+  const size_t off_exp = cv.take(size_t(F0) * S * sizeof(int));
+  const size_t off_live = cv.take(size_t(F0) * S * sizeof(int));
+  const size_t off_r = cv.take(size_t(mvdr_triangle_bytes(M, H)));
+  const size_t off_w = d_weights ? 0 : cv.take(wbytes);
+  char* blk = nullptr;
+  PAL_TRY(scratch(kWsBeam, cv.off, &blk));
+  cd* X = reinterpret_cast<cd*>(blk + off_x);
+  cd* Y = reinterpret_cast<cd*>(blk + off_y);
+  int* flags = reinterpret_cast<int*>(blk + off_flags);
+  int* row_exp = reinterpret_cast<int*>(blk + off_exp);
+  int* beam_live = reinterpret_cast<int*>(blk + off_live);
+  cd* R = reinterpret_cast<cd*>(blk + off_r);
+  const Conv& c = pl->inv;
+  const int fl = int(0.01 * double(L));
+  const double val = 1.0 / (double(2 * L) * (1.0 / fs));
+  const unsigned bin_tiles = unsigned((H + kMvdrBins - 1) / kMvdrBins);
+  const int chunk_bins = int((H + 7) / 8);
+  int ti, tj;
+  mvdr_tile_shape(mvdr_tile, &ti, &tj);
+  for (int g = 0; g < G; ++g) {
+    const double* dl = d_delays + size_t(g) * S * M;
+    const double* gn = d_gains + size_t(g) * S * M;
+    cd* W = d_weights ? reinterpret_cast<cd*>(d_weights) + size_t(g) * S * M * H : reinterpret_cast<cd*>(blk + off_w);
+    for (int sl = 0; sl < nsl; ++sl) {
+      int f0, F;
+      mvdr_slice_of(g, sl, Q, F0, &f0, &F);
+      {
+        ProfScope ps(e, "mvdr_forward_spectra_1");
+        PAL_TRY(forward_spectra(*pl, d_frames + size_t(f0) * M * L, size_t(L), F * M, L, X, flags));
+      }
+      ProfScope ps(e, "k_mvdr_cov");
+      const dim3 cov_grid(bin_tiles, unsigned(mvdr_tile_count(M, ti, tj)));
+      if (ti == 4) k_mvdr_cov<4, 4><<<cov_grid, dim3(kMvdrBins), 0, stream>>>(X, M, int(H), F, sl == 0, R);
+      else k_mvdr_cov<8, 4><<<cov_grid, dim3(kMvdrBins), 0, stream>>>(X, M, int(H), F, sl == 0, R);
+      PAL_TRY(check(hipGetLastError(), "k_mvdr_cov"));
+    }
+    {
+      ProfScope ps(e, "k_mvdr_weights");
+      k_mvdr_weights<<<dim3(unsigned(8 * chunk_bins)), dim3(64), mvdr_weights_lds(M), stream>>>(R, dl, gn, M, L, S, val, loading, chunk_bins, W);
+      PAL_TRY(check(hipGetLastError(), "k_mvdr_weights"));
+    }
+    for (int sl = 0; sl < nsl; ++sl) {
+      int f0, F;
+      mvdr_slice_of(g, sl, Q, F0, &f0, &F);
+      if (nsl > 1) {                                          // a group of one slice still holds its spectra
+        ProfScope ps(e, "mvdr_forward_spectra_2");
+        PAL_TRY(forward_spectra(*pl, d_frames + size_t(f0) * M * L, size_t(L), F * M, L, X, flags));
+      }
+      const int rows = F * S;
+      {
+        ProfScope ps(e, "k_mvdr_apply");
+        const unsigned row_blocks = unsigned((rows + 255) / 256);
+        k_mvdr_rows<<<dim3(row_blocks), dim3(256), 0, stream>>>(flags, gn, M, S, rows, row_exp, beam_live);
+        PAL_TRY(check(hipGetLastError(), "k_mvdr_rows"));
+        if (S == 1)
+          k_mvdr_apply<1, 8><<<dim3(bin_tiles, unsigned((F + 7) / 8), 1), dim3(kMvdrBins), 0, stream>>>(X, W, M, int(H), S, F, beam_live, Y, row_exp);
+        else if (S == 2)
+          k_mvdr_apply<2, 4><<<dim3(bin_tiles, unsigned((F + 3) / 4), 1), dim3(kMvdrBins), 0, stream>>>(X, W, M, int(H), S, F, beam_live, Y, row_exp);
+        else
+          k_mvdr_apply<4, 4><<<dim3(bin_tiles, unsigned((F + 3) / 4), unsigned((S + 3) / 4)), dim3(kMvdrBins), 0, stream>>>(X, W, M, int(H), S, F, beam_live, Y, row_exp);
+        PAL_TRY(check(hipGetLastError(), "k_mvdr_apply"));
+        k_mvdr_close<<<dim3(row_blocks), dim3(256), 0, stream>>>(rows, row_exp);
+        PAL_TRY(check(hipGetLastError(), "k_mvdr_close"));
+      }
+      double* out = d_out + size_t(f0) * S * L;
+      cd* work = nullptr;
+      PAL_TRY(scratch(kWsWork, size_t(chunk) * c.M() * sizeof(cd), &work));
+      ProfScope ps(e, "mvdr_inverse");
+      const int ntr = (rows + 1) / 2;
+      for (int t0 = 0; t0 < ntr; t0 += chunk) {
+        const int n = ntr - t0 < chunk ? ntr - t0 : chunk;
+        const int r0 = 2 * t0;
+        MvdrLoader ld{Y, row_exp, rows, L, r0, pl->w};
+        SimStorer st{out, size_t(L), rows, L, L, fl, r0, fl > 1 ? 1.0 / double(fl - 1) : 0.0, fl > 1 ? -1.0 / double(fl - 1) : 0.0,
+                     pl->w, row_exp, 1};
+        PAL_TRY(launch_cols_fwd(e, c, n, ld, work));
+        PAL_TRY(launch_rows(e, c, n, work, true, 1.0));
+        PAL_TRY(launch_cols_inv(e, c, n, work, st));
+      }
+      k_steer_silence<<<dim3(unsigned(rows)), dim3(256), 0, stream>>>(out, L, beam_live);
+      PAL_TRY(check(hipGetLastError(), "k_steer_silence"));
+    }
+  }
+  return PAL_OK;
+}
+
 }  // namespace pal
 
 using namespace pal;
@@ -480,6 +609,34 @@ int pal_separate(pal_handle h, const double* frames, int B, int M, int L, double
   PAL_TRY(e->check(hipStreamSynchronize(e->stream), "upload sync"));
   PAL_TRY(e->separate_dev(dx, B, M, L, fs, dt, dt + ntab, S, loading, dout));
   DOWN(out, dout, nout * sizeof(double));
+  return pal_synchronize(h);
+}
+
+int pal_mvdr_dev(pal_handle h, const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_gains, int G,
+                 int S, double loading, double* d_out, double* d_weights) {
+  ENGINE(h);
+  return e->mvdr_dev(d_frames, B, M, L, fs, d_delays, d_gains, G, S, loading, d_out, d_weights);
+}
+
+int pal_mvdr(pal_handle h, const double* frames, int B, int M, int L, double fs, const double* delays, const double* gains, int G, int S,
+             double loading, double* out, double* weights) {
+  ENGINE(h);
+  if (!frames || !delays || !gains || !out) return e->fail(PAL_ERR_INVALID, "NULL buffer");
+  PAL_TRY(e->mvdr_check(B, M, L, fs, G, S, loading));
+  const size_t nin = size_t(B) * M * L, ntab = size_t(G) * S * M, nout = size_t(B) * S * L;
+  const size_t nw = weights ? 2 * ntab * (size_t(L) + 1) : 0;
+  PAL_TRY(check_steer_tables(e, delays, gains, ntab, fs, L));
+  double *dx = nullptr, *dt = nullptr, *dout = nullptr;
+  PAL_TRY(e->scratch(kWsStageIn, nin * sizeof(double), &dx));
+  PAL_TRY(e->scratch(kWsStageTable, 2 * ntab * sizeof(double), &dt));
+  PAL_TRY(e->scratch(kWsStageOut, (nout + nw) * sizeof(double), &dout));
+  UP(dx, frames, nin * sizeof(double));
+  UP(dt, delays, ntab * sizeof(double));
+  UP(dt + ntab, gains, ntab * sizeof(double));
+  PAL_TRY(e->check(hipStreamSynchronize(e->stream), "upload sync"));
+  PAL_TRY(e->mvdr_dev(dx, B, M, L, fs, dt, dt + ntab, G, S, loading, dout, weights ? dout + nout : nullptr));
+  DOWN(out, dout, nout * sizeof(double));
+  if (weights) DOWN(weights, dout + nout, nw * sizeof(double));
   return pal_synchronize(h);
 }
 

@@ -93,7 +93,7 @@ enum Ws : int {
   kWsConsensus = 29,   // the consensus (consensus.hip): frame lengths, candidate cubes, chosen-lag matrices, three selections, two vote tables
   kWsCandK = 30, kWsCandH = 31,   // the selected peaks of a launch group per stream slot (PAL_MAX_PEAKS indices / heights per row), compacted into a CandOut
   kWsSrp = 32,         // SRP (srp.hip): a frame slice's correlation rows and one-peak table (the strips call); microphones, direction tables, clip counters, peak marks, the map when the caller takes none (SrpCarve: every other call)
-  kWsBeam = 33,        // the delay-and-sum beamformer (beamform.hip): a frame slice's spectra and row flags, its beam spectra, exponents and live marks
+  kWsBeam = 33,        // the delay-and-sum beamformer (beamform.hip): a frame slice's spectra and row flags, its beam spectra, exponents and live marks; MVDR adds a group's covariance triangle and weights
   kWsCount = 34
 };
 constexpr Ws peak_scratch_slot(int slot) { return slot == 0 ? kWsPeaks0 : (slot == 1 ? kWsPeaks1 : kWsPeaks2); }
@@ -288,7 +288,13 @@ struct Engine {
                    double loading, double* d_out);
   int beams_dev(const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_weights, int S,
                 double* d_out, bool solve, double loading);
-  int beam_slice = 0;              // PAL_BEAM_SLICE=<frames>: frames per slice of steer_sum_dev and separate_dev (0: as many as keep the slice's spectra near 1 GiB)
+  // the MVDR beams of the same frames in G groups of B / G (beamform.py, mvdr): delays / gains[G][S][M], weights from each group's
+  // covariance; M <= 64, loading > 0; d_weights: NULL or [G][S][M][L + 1] complex
+  int mvdr_check(int B, int M, int L, double fs, int G, int S, double loading);
+  int mvdr_dev(const double* d_frames, int B, int M, int L, double fs, const double* d_delays, const double* d_gains, int G, int S,
+               double loading, double* d_out, double* d_weights);
+  int mvdr_tile = 0;               // PAL_MVDR_TILE=44: 4 x 4 microphone pairs per workgroup of k_mvdr_cov (default 8 x 4; the bytes do not depend on it)
+  int beam_slice = 0;              // PAL_BEAM_SLICE=<frames>: frames per slice of steer_sum_dev, separate_dev and mvdr_dev (0: as many as keep the slice's spectra near 1 GiB)
   int32_t* solve_idx = nullptr;    // device table pair -> i | j << 16 of the last microphone count
   int solve_idx_M = 0;
   // resample.hip: the right wing of the interpolation filter as pal_resample_set_filter received it, and the ratio whose scaled

@@ -376,6 +376,8 @@ int pal_create(int device, pal_handle* out) {
   if (env && atoi(env) >= 2) e->max_plans = atoi(env);
   env = getenv("PAL_BEAM_SLICE");
   if (env && atoi(env) >= 1) e->beam_slice = atoi(env);
+  env = getenv("PAL_MVDR_TILE");
+  if (env) e->mvdr_tile = atoi(env);
   *out = reinterpret_cast<pal_handle>(e);
   return PAL_OK;
 }

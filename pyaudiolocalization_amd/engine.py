@@ -783,6 +783,48 @@ class Engine:
         self._check(self._lib.pal_separate_dev(self._h, C.c_void_p(d_frames), int(b), int(m), int(length), float(fs), C.c_void_p(d_delays),
                                                C.c_void_p(d_gains), int(s), float(loading), C.c_void_p(d_out)))
 
+    def mvdr(self, frames, fs, delays, gains=None, loading=0.1, groups=1, return_weights=False):
+        """MVDR beams: frames[B][M][L] in ``groups`` groups of B / groups consecutive frames, delays[G][S][M] (seconds) and
+        gains[G][S][M] (None: 1) -> out[B][S][L] (rule: beamform.mvdr): the weights come from each group's own covariance under the
+        diagonal loading ``loading * tr(R) / M``.  M <= 64, loading > 0.  delays[S][M] serves one group.  ``return_weights``: ->
+        (out, w[G][S][M][L + 1] complex), the bins 0 .. L of beamform.mvdr_weights."""
+        x, d = f64(frames), f64(delays)
+        if d.ndim == 2:
+            d = d[None]
+        groups = int(groups)
+        if x.ndim != 3 or d.ndim != 3 or d.shape[2] != x.shape[1]:
+            raise ValueError("frames must be [B][M][L] with delays[G][S][M] (or [S][M] for one group)")
+        b, m, length = x.shape
+        if groups < 1 or b % groups or d.shape[0] != groups:
+            raise ValueError("groups must be >= 1, divide the number of frames and count the steering tables")
+        if gains is None:
+            g = np.ones(d.shape)
+        else:
+            g = f64(gains)
+            if g.ndim == 2:
+                g = g[None]
+            if g.shape != d.shape:
+                raise ValueError("gains must have the shape of delays")
+        s = d.shape[1]
+        if m < 1 or s < 1 or b < 1:
+            raise ValueError("need at least one frame, one microphone and one steering point")
+        if length < 100:
+            raise ValueError("steering needs at least 100 samples (the fade window of fractional_delay)")
+        out = np.empty((b, s, length))
+        w = np.empty((groups, s, m, length + 1), dtype=np.complex128) if return_weights else None
+        self._check(self._lib.pal_mvdr(self._h, x.ctypes.data, b, m, length, float(fs), d.ctypes.data, g.ctypes.data, groups, s,
+                                       float(loading), out.ctypes.data, w.ctypes.data if return_weights else None))
+        return (out, w) if return_weights else out
+
+    def mvdr_dev(self, d_frames: int, b: int, m: int, length: int, fs: float, d_delays: int, d_gains: int, groups: int, s: int,
+                 loading: float, d_out: int, d_weights: int = 0) -> None:
+        """Engine.mvdr on buffers in HBM: d_frames[b][m][length], d_delays / d_gains[groups][s][m] -> d_out[b][s][length] and, where
+        d_weights is not 0, d_weights[groups][s][m][length + 1] complex; asynchronous, refused table entries and non-finite samples
+        surface in synchronize()."""
+        self._check(self._lib.pal_mvdr_dev(self._h, C.c_void_p(d_frames), int(b), int(m), int(length), float(fs), C.c_void_p(d_delays),
+                                           C.c_void_p(d_gains), int(groups), int(s), float(loading), C.c_void_p(d_out),
+                                           C.c_void_p(d_weights or None)))
+
     def steer_dev(self, d_frames: int, b: int, m: int, length: int, fs: float, d_delays: int, d_weights: int, s: int, d_out: int) -> None:
         """Engine.steer on buffers in HBM: d_frames[b][m][length], d_delays / d_weights[b][s][m] -> d_out[b][s][length]; asynchronous,
         refused table entries and non-finite samples surface in synchronize()."""

@@ -346,6 +346,27 @@ def separate_device(frames, mic_positions, fs, c, points=None, directions=None, 
     return out[0] if one else out
 
 
+def mvdr_device(frames, mic_positions, fs, c, points=None, directions=None, gains=None, loading=0.1, groups=1, calib_delays=None,
+                engine=None):
+    """frames[B][M][L] -> out[B][S][L]: the MVDR beams at ``points`` or ``directions`` (Engine.mvdr, rule: beamform.mvdr).  The frames
+    are ``groups`` groups of B / groups consecutive frames; a group's frames are the snapshots of one covariance and share one
+    steering table, so ``points`` / ``directions`` are [G][S][3], or [S][3] for every group, or SRP records [G][S].  ``gains``:
+    [G][S][M] (or what broadcasts to it), by default 1; an absent record or a point with a non-finite coordinate gets gains of 0, a
+    row of zeros.  ``loading``: the diagonal loading relative to tr(R) / M (> 0).  Unlike separate_device the beam is told nothing
+    about the other sources: what is stationary over a group's frames and does not arrive with the target's delays is cancelled from
+    the data.  M <= 64.  frames[M][L] is one group of one frame and gives out[S][L]."""
+    x = np.ascontiguousarray(frames, dtype=np.float64)
+    one = x.ndim == 2
+    if one:
+        x = x[None]
+    groups = int(groups)
+    if x.ndim != 3 or groups < 1 or x.shape[0] % groups:
+        raise ValueError("frames must be [B][M][L] in groups that divide B")
+    _, delays, g, _ = _beam_tables(x[:groups], mic_positions, c, points, directions, gains, calib_delays, 1.0)
+    out = (engine or default_engine()).mvdr(x, fs, delays, g, loading, groups)
+    return out[0] if one else out
+
+
 def localize_sound_source(config, calibration_data=None, audio_files=None, use_simulation=True, show_plots=True):
     fs = config["fs"]
     duration = config["duration"]
